@@ -1,7 +1,11 @@
 """Headline benchmark: ML-20M-shaped I-AutoRec training steps on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs) and prints the
+line.  --full adds the side legs to the same line: the CPU baseline, the test-split masked RMSE, the exact-fp32
+mode, a whole training epoch, the other BASELINE configs and, at N>1, the run's self-checks against one GPU.
 
 One step = one pass of the hot path over one batch resident in HBM: the epoch's batch
 preparation for the timed batches, the row-gather encoder, the row-gather decoder with the hidden layer's
@@ -44,6 +48,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side legs (--cpu-baseline, --rmse, --fp32-steps, --epoch, --configs and, at N>1, "
+                         "the parity / consistency checks and the same-batch one-GPU point); a plain run skips them all")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one left with the caller to DIR/<name>.npy "
+                         "(dump_outputs)")
     ap.add_argument("--config", default="ml20m")
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--skew", type=float, default=0.0,
@@ -81,7 +91,47 @@ def parse():
                     help="dp: reduce-scatter + sharded optimizer + all-gather, or one all-reduce + full optimizer")
     ap.add_argument("--dp-grad-dtype", default="float32", choices=["float32", "bfloat16"],
                     help="dp sharded: gradient dtype of the reduce-scatter")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run does only what the headline needs: the side legs' switches count under --full alone
+        args.cpu_baseline = args.fp32_steps = args.epoch = args.rmse = args.configs = 0
+    return args
+
+
+DUMP_MAX_ELEMS = 1 << 21       # a dumped kernel's elements (8 MB in float32); a larger one is sampled
+
+
+def dump_outputs(path, eng, stats, steps, write=True):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as path/<name>.npy --
+    every layer's kernel and bias in get_weights()' Keras layout (W<i>, b<i>: float32; a kernel of more than
+    DUMP_MAX_ELEMS elements as a fixed, seeded sample along its longer side: input rows of the encoder, output
+    columns of the decoder) and the stats rows take_stats() returned for the timed steps (float64:
+    timed_stats [steps, 4] = SSE, SAE, target count, l2 penalty of every step; last_step_stats = the last
+    step's row with its per-batch-row SSE).  The data, the weights and the dropout streams are seeded, so two
+    runs with the same arguments dump the same step.  Under ZeRO-1 the fp32 masters are gathered first (a
+    collective: every rank calls this, `write` is rank 0; a column shard dumps rank 0's columns)."""
+    if eng.master_sync is not None:
+        eng.master_sync()
+    rng = np.random.RandomState(20)
+    out = {"timed_stats": np.ascontiguousarray(stats[-steps:, :4], dtype=np.float64),
+           "last_step_stats": np.ascontiguousarray(stats[-1], dtype=np.float64)}
+    for i, b in enumerate(eng.b):
+        rows, cols = eng._row_map(i), np.arange(eng.real_dims[i + 1])
+        kv = eng._keras_view(i)
+        by_rows = len(rows) >= len(cols)
+        if len(rows) * len(cols) > DUMP_MAX_ELEMS:
+            if by_rows:
+                rows = rows[np.sort(rng.choice(len(rows), DUMP_MAX_ELEMS // len(cols), replace=False))]
+            else:
+                cols = cols[np.sort(rng.choice(len(cols), DUMP_MAX_ELEMS // len(rows), replace=False))]
+        r, c = torch.as_tensor(rows, device=eng.dev), torch.as_tensor(cols, device=eng.dev)
+        w = kv.index_select(0, r).index_select(1, c) if by_rows else kv.index_select(1, c).index_select(0, r)
+        out["W%d" % i] = w.float().cpu().numpy()
+        out["b%d" % i] = b[: eng.real_dims[i + 1]].float().cpu().numpy()
+    if write:
+        os.makedirs(path, exist_ok=True)
+        for name, a in out.items():
+            np.save(os.path.join(path, name + ".npy"), a)
 
 
 class _NoComm:
@@ -491,7 +541,9 @@ def jester_main(args):
     else:
         dom_timed = e.phase_times_ms().get(dom) if dom else None
     e.enable_timers(False)
-    e.take_stats()
+    stats = e.take_stats()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, e, stats, args.steps)
     ms = elapsed / args.steps * 1e3
     # algorithmic work per step: dims 200 -> 256 -> 256 -> 100, no input gradient
     dims = [2 * N, H, H, N]
@@ -672,7 +724,7 @@ def main():
         if (world > 1 and not fp) else None
     nnz_of = gen.nnz1
     same_batch = None
-    if fp and world > 1 and rank == 0 and not args.emulate_shards:
+    if args.full and fp and world > 1 and rank == 0 and not args.emulate_shards:
         same_batch = same_batch_one_gpu(args, data_full, n_rows, B * world, dev)
     setup_s = time.time() - t0
 
@@ -689,7 +741,7 @@ def main():
 
     # N > 1: this run's first steps against one GPU (feature layout), before the warm-up
     parity = None
-    if fp and world > 1 and not args.emulate_shards:
+    if args.full and fp and world > 1 and not args.emulate_shards:
         parity = n_rank_parity(args, m, eng, step, data_full, n_rows, Bg, shard, dev, rank, world, batches, gen)
 
     # warm-up (untimed): every phase bracketed by HIP events -> per-phase breakdown and the dominant
@@ -749,7 +801,7 @@ def main():
                   for k, v in eng.step_paths.items()}                            # steps (and why)
     dom_timed = eng.phase_times_ms().get(dom) if dom else None
     eng.timers = None
-    if dpo is not None:
+    if args.full and dpo is not None:
         parity = replica_consistency(eng, dev, world)
     row_skip_used = eng._rtag_live          # (the eval batches below reset it)
     tot = torch.tensor([elapsed, float(nnz)], device=dev, dtype=torch.float64)
@@ -759,7 +811,9 @@ def main():
         nsum = tot[1:].clone()
         torch.distributed.all_reduce(nsum, op=torch.distributed.ReduceOp.SUM)
         elapsed, nnz = float(tmax.item()), float(nsum.item())
-    eng.take_stats()
+    stats = eng.take_stats()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, stats, args.steps, write=rank == 0)
 
     # masked RMSE on the test split (train.py:225-255, fused form)
     rmse = None
@@ -782,13 +836,13 @@ def main():
     live = 1.0
     if row_skip_used and args.optimizer == "adagrad":
         tr = data.train
-        fr = []
-        for i in range(args.steps):
-            rows = np.asarray(gen.rows_host[batches[(args.warmup + i) % len(batches)]])
+        fr = {}                               # by batch: the timed steps cycle through the epoch's batches
+        for bi in set(batches[(args.warmup + i) % len(batches)] for i in range(args.steps)):
+            rows = np.asarray(gen.rows_host[bi])
             rows = rows[rows >= 0]
             cols = np.concatenate([tr.col[tr.row_ptr[r]:tr.row_ptr[r + 1]] for r in rows])
-            fr.append(len(np.unique(cols)) / Nl)
-        live = float(np.mean(fr))
+            fr[bi] = len(np.unique(cols)) / Nl
+        live = float(np.mean([fr[batches[(args.warmup + i) % len(batches)]] for i in range(args.steps)]))
     opt_b = OPT_STATE_BYTES[args.optimizer]
     # weight operands: the compute-dtype shadow (2 B) written by the optimizer epilogue, fp32 in fp32 mode
     w_b = 4 if args.dtype == "float32" else 2

@@ -6,7 +6,7 @@ set -e -o pipefail
 O=gpurun_out/${1:-cfg}; mkdir -p $O
 run() {   # name, timeout, bench args...
   local n=$1 t=$2; shift 2
-  timeout -k 10 $t python bench.py "$@" > $O/$n.log 2>&1
+  timeout -k 10 $t python bench.py --full "$@" > $O/$n.log 2>&1
   grep '^{' $O/$n.log | tail -1 > $O/$n.json
   echo "$n done"
 }

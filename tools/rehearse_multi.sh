@@ -15,7 +15,7 @@ export OCF_REHEARSAL=1
 port=29531
 for par in $layouts; do
     timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-        --master-port $port bench.py --gpus 2 --parallel $par "${extra[@]}" \
+        --master-port $port bench.py --full --gpus 2 --parallel $par "${extra[@]}" \
         > "$out/bench_$par.json" 2> "$out/bench_$par.err" || { echo "rehearsal $par failed: $?"; tail -5 "$out/bench_$par.err"; exit 1; }
     port=$((port + 1))
     cat "$out/bench_$par.json"
