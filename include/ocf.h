@@ -350,6 +350,58 @@ typedef struct OcfGemmArgs {
 int ocf_gemm(const OcfGemmArgs* args, void* stream);
 
 /*
+ * ocf_topk -- recommendations straight from the decoder GEMM: for every batch row m < m_real the k largest
+ *   score[m][n] = h[m] . W[n] + bias[n]     over the eligible columns n
+ * with their columns, without a [M][N] score array anywhere (global memory or workspace).  A column is eligible
+ * when n < n_real and it is not excluded for row m.  Every score is bit-identical to what ocf_gemm's
+ * OCF_EPI_PREDICT writes from the same operands (the same MFMA K-loop per 128x128 tile, no split-K).
+ * Order: descending score, equal scores by ascending column -- deterministic, independent of `groups`.  A row
+ * with fewer than k eligible columns ends in (index -1, value -inf).  NaN scores: behaviour is not defined.
+ * Two launches: the select kernel (a workgroup owns a row tile and a contiguous run of column tiles, keeps a
+ * running top-k per batch row against its k-th value, writes one candidate list per (row, group)), then the
+ * merge kernel (a wave per batch row merges the groups' lists; optionally scores the list against held-out
+ * entries).  No grid barrier, no wait between workgroups.
+ */
+#define OCF_TOPK_MAX_K 128
+typedef struct OcfTopkArgs {
+  int compute_dtype;        /* OCF_DT_*: the MFMA operand type                                              */
+  const void* h;            /* [M][ldh] last hidden activations in the compute dtype                        */
+  int64_t ldh;
+  const void* W;            /* decoder weight stored [N][ldw]: fp32 master, or its compute-dtype shadow     */
+  int w_dtype;              /* OCF_DT_F32 or compute_dtype                                                  */
+  int64_t ldw;
+  int w_blocked;            /* the 16-bit shadow is stored 64x64-blocked (OcfGemmArgs b_blocked)            */
+  const float* bias;        /* [N]                                                                          */
+  int M, N, K;              /* padded batch rows, output columns, hidden width: multiples of 128            */
+  int m_real, n_real;       /* real batch rows (<= M) and columns (<= N)                                    */
+  int k;                    /* list length, 1 .. OCF_TOPK_MAX_K                                             */
+  int groups;               /* column groups per batch row: 0 = the library's choice; more than N / 128 = N / 128 */
+  /* exclusion, row-segment form (nullable ex_rows): batch row m excludes every entry of row ex_rows[m] (-1 =
+   * none) of a CSR given by its column-sorted tile index (RatingsCSR.tile_index): row pointers ex_rp, per-row
+   * tile pointers ex_tptr [rows][ex_ntiles + 1], columns ex_col.  Duplicates are fine; no flag array. */
+  const int32_t* ex_rows; const int64_t* ex_rp; const int32_t* ex_tptr; const int32_t* ex_col; int ex_ntiles;
+  /* exclusion, dense form (nullable ex_mask): fp32, nonzero = excluded; batch row m at row ex_mrows[m]
+   * (nullable: m) of [*][ld_ex], columns < n_real.  At most one of the two forms. */
+  const float* ex_mask; int64_t ld_ex; const int64_t* ex_mrows;
+  int32_t* out_idx;         /* [m_real][ld_out] columns, -1 past the eligible ones                          */
+  float* out_val;           /* [m_real][ld_out] scores, -inf past the eligible ones                         */
+  int64_t ld_out;           /* >= k                                                                         */
+  void* work;               /* device scratch of ocf_topk_workspace(args) bytes: the candidate lists,
+                               [M][groups][k] x 8 B plus a fixed header -- never anything of size M x N     */
+  int64_t work_bytes;
+  /* ranking statistics (nullable rel_rows): the held-out entries of batch row m are row rel_rows[m] (-1 = none)
+   * of a CSR in column-sorted order (rel_rp, rel_col, rel_val: RatingsCSR.tile_index); an entry is relevant when
+   * rel_val >= rel_min.  row_rank[m] = {hits, dcg, n_relevant, 0}: the returned columns that are relevant, the sum
+   * of 1 / log2(j + 2) over the list positions j holding a relevant column, the row's relevant columns. */
+  const int32_t* rel_rows; const int64_t* rel_rp; const int32_t* rel_col; const float* rel_val;
+  float rel_min;
+  float* row_rank;          /* [m_real][4]; required with rel_rows                                          */
+} OcfTopkArgs;
+/* bytes of OcfTopkArgs.work for these arguments (host only, no device access); -1 + ocf_last_error on bad ones */
+int64_t ocf_topk_workspace(const OcfTopkArgs* args);
+int ocf_topk(const OcfTopkArgs* args, void* stream);
+
+/*
  * ocf_gemm_pair -- ocf_gemm(a) then ocf_gemm(b) for the two weight updates of a one-hidden-layer step
  * (a = the output layer, with the decoder's folded row reduction jr; b = the input layer, whose operand B
  * and job inputs that reduction writes: train.py:50-51 for both kernels).  When both take the row-stream

@@ -130,6 +130,21 @@ class OcfGemmArgs(ctypes.Structure):
     ]
 
 
+TOPK_MAX_K = 128               # ocf.h OCF_TOPK_MAX_K
+
+
+class OcfTopkArgs(ctypes.Structure):
+    """ocf.h OcfTopkArgs: the k best decoder scores per batch row (ocf_topk)"""
+    _fields_ = [
+        ("compute_dtype", I32), ("h", P), ("ldh", I64), ("W", P), ("w_dtype", I32), ("ldw", I64), ("w_blocked", I32),
+        ("bias", P), ("M", I32), ("N", I32), ("K", I32), ("m_real", I32), ("n_real", I32), ("k", I32), ("groups", I32),
+        ("ex_rows", P), ("ex_rp", P), ("ex_tptr", P), ("ex_col", P), ("ex_ntiles", I32),
+        ("ex_mask", P), ("ld_ex", I64), ("ex_mrows", P),
+        ("out_idx", P), ("out_val", P), ("ld_out", I64), ("work", P), ("work_bytes", I64),
+        ("rel_rows", P), ("rel_rp", P), ("rel_col", P), ("rel_val", P), ("rel_min", F32), ("row_rank", P),
+    ]
+
+
 class OcfPairSync(ctypes.Structure):
     """ocf.h OcfPairSync: ocf_gemm_pair's hand-off counter (device word + its host-side running count)"""
     _fields_ = [("word", P), ("count", U64)]
@@ -235,6 +250,8 @@ SIGNATURES = {
     "ocf_dense_targets": (I32, [P, P, I64, I32, I32, I32, P, P, P, P, P, P, P, P]),
     "ocf_pack_input": (I32, [P, P, P, I64, I32, I32, P, I32, I64, I64, I32, P, P]),
     "ocf_gemm": (I32, [ctypes.POINTER(OcfGemmArgs), P]),
+    "ocf_topk": (I32, [ctypes.POINTER(OcfTopkArgs), P]),
+    "ocf_topk_workspace": (I64, [ctypes.POINTER(OcfTopkArgs)]),
     "ocf_gemm_pair": (I32, [ctypes.POINTER(OcfGemmArgs), ctypes.POINTER(OcfGemmArgs), P, P]),   # P: OcfPairSync*
     "ocf_train_step_rows": (I32, [ctypes.POINTER(OcfRowStepArgs), P]),
     "ocf_rank_step": (I32, [ctypes.POINTER(OcfRankStepArgs), I32, P]),

@@ -1125,6 +1125,103 @@ class Engine:
                    ld_pmask=out_mask.stride(0) if out_mask is not None else 0, out=out, ld_out=out.stride(0),
                    m_real=self.B, n_real=self.N)
 
+    def _finish_deferred_encoder(self):
+        """forward() on the row-gather path may leave the encoder to the decoder gather (_forward_gather,
+        self._enc_fused): run it here in its separate form (ocf_gather_encoder + ocf_rows_reduce with the hidden
+        epilogue), so that h[0] exists for a consumer that is not the decoder gather.  fuse_enc_epilogue is not
+        touched."""
+        ef, self._enc_fused = self._enc_fused, None
+        if ef is None:
+            return
+        tab, Hp0 = ef["tab"], self.Hp[0]
+        call("ocf_gather_encoder", ef["args"], cur_stream())
+        r = self._reduce_args(tab, self._gbuf["part_enc"], Hp0, _lib.REDUCE_BIAS_ACT)
+        r.bias, r.act, r.keep, r.seed, r.stream = ptr(self.b[0]), self.act, ef["keep"], self.seed, ef["stream"]
+        r.mask_out = ptr(self.mask[0]) if ef["keep"] < 1 else None
+        r.a_out, r.h_out, r.h_dtype, r.n_real = ptr(self.a[0]), ptr(self.h[0]), self.cdt, self.H[0]
+        call("ocf_rows_reduce", r, cur_stream())
+
+    def topk(self, k, exclude=None, relevance=None, groups=None, out=None):
+        """The k best output columns of every batch row (ocf_topk), after forward(training=False): device tensors
+        idx [B, k] int32 (-1 past the eligible columns) and val [B, k] fp32 (-inf there), in descending score,
+        equal scores by ascending column; every score bit-identical to predict_dense's.  No [B, N] array is
+        written.
+
+        exclude: None; a device fp32 [B, N] tensor (nonzero = excluded; dict(ex_mask=..., ex_mrows=...) gathers
+        its rows by index); or the row-segment form dict(ex_rows, ex_rp, ex_tptr, ex_col, ex_ntiles) -- a CSR's
+        column-sorted tile index (data_reader._DeviceCSR.tiles), every entry of batch row b's CSR row excluded.
+        relevance: dict(rel_rows, rel_rp, rel_col, rel_val[, rel_min]) -- held-out entries in column-sorted order;
+        then a third tensor row_rank [B, 4] = (hits, dcg, n_relevant, 0) per row is returned.
+        groups: column groups per batch row (None: the library's choice).
+        out: (idx, val) tensors to write into (rows >= B and columns >= k of them are left alone).
+
+        Nothing of the training state changes: no stats row, no step count, dropout off.  The candidate workspace is
+        the engine's own tensor, outside the buffers whose growth invalidates the one-call step's plan."""
+        if self.comm is not None:
+            raise ValueError("topk: a feature-parallel engine holds a column shard; its per-shard lists would need "
+                             "a cross-rank merge, which is not built")
+        k = int(k)
+        if self.master_sync is not None:
+            self.master_sync()
+        self._finish_deferred_encoder()
+        L = len(self.H)
+        Wt, wdt = self._wop(L)
+        a = _lib.OcfTopkArgs()
+        a.compute_dtype = self.cdt
+        a.h, a.ldh = ptr(self.h[L - 1]), self.Hp[L - 1]
+        a.W, a.w_dtype, a.ldw, a.w_blocked = ptr(Wt), wdt, Wt.shape[1], self._wblk(L)
+        a.bias = ptr(self.b[L])
+        a.M, a.N, a.K, a.m_real, a.n_real = self.Bp, self.Np, self.Hp[L - 1], self.B, self.N
+        a.k, a.groups = k, int(groups or 0)
+        keep = [exclude, relevance]
+        if torch.is_tensor(exclude):
+            exclude = dict(ex_mask=exclude)
+        if exclude is not None:
+            if "ex_mask" in exclude:
+                m = exclude["ex_mask"]
+                if not (torch.is_tensor(m) and m.is_cuda and m.dtype == torch.float32 and m.dim() == 2
+                        and m.shape[1] >= self.N and m.stride(1) == 1):
+                    raise ValueError("topk: the dense exclusion is a device fp32 [rows, >= %d] tensor" % self.N)
+                rows = exclude.get("ex_mrows")
+                if rows is None and m.shape[0] < self.B:
+                    raise ValueError("topk: the dense exclusion has %d rows, the batch %d" % (m.shape[0], self.B))
+                a.ex_mask, a.ld_ex, a.ex_mrows = ptr(m), m.stride(0), ptr(rows)
+            else:
+                a.ex_rows, a.ex_rp, a.ex_tptr, a.ex_col = [
+                    v.data_ptr() if torch.is_tensor(v) else v
+                    for v in (exclude["ex_rows"], exclude["ex_rp"], exclude["ex_tptr"], exclude["ex_col"])]
+                a.ex_ntiles = int(exclude["ex_ntiles"])
+        if out is not None:
+            idx, val = out
+            for t, dt in ((idx, torch.int32), (val, torch.float32)):
+                if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.dim() == 2 and t.shape[0] >= self.B
+                        and t.shape[1] >= k and t.stride(1) == 1 and t.stride(0) == idx.stride(0)):
+                    raise ValueError("topk: out = (int32, fp32) device tensors [>= %d, >= %d] with one row stride"
+                                     % (self.B, k))
+        else:
+            idx = torch.empty(self.B, k, device=self.dev, dtype=torch.int32)
+            val = torch.empty(self.B, k, device=self.dev, dtype=torch.float32)
+        a.out_idx, a.out_val, a.ld_out = ptr(idx), ptr(val), idx.stride(0)
+        rank = None
+        if relevance is not None:
+            a.rel_rows, a.rel_rp, a.rel_col, a.rel_val = [
+                v.data_ptr() if torch.is_tensor(v) else v
+                for v in (relevance["rel_rows"], relevance["rel_rp"], relevance["rel_col"], relevance["rel_val"])]
+            rm = relevance.get("rel_min")
+            a.rel_min = float("-inf") if rm is None else float(rm)
+            rank = torch.empty(self.B, 4, device=self.dev, dtype=torch.float32)
+            a.row_rank = ptr(rank)
+        nb = int(_lib.load().ocf_topk_workspace(ctypes.byref(a)))
+        if nb < 0:
+            raise _lib.OcfError("ocf_topk_workspace failed: %s" % _lib.load().ocf_last_error().decode())
+        w = getattr(self, "_topk_work", None)
+        if w is None or w.numel() < nb:
+            w = self._topk_work = torch.empty(nb, device=self.dev, dtype=torch.uint8)
+        a.work, a.work_bytes = ptr(w), w.numel()
+        call("ocf_topk", a, cur_stream())
+        del keep
+        return (idx, val) if rank is None else (idx, val, rank)
+
     # ---------------------------------------------------------------- backward + update
     def backward_update(self, grads_out=None):
         """Backward pass; with grads_out=None the optimizer is fused into the weight-gradient GEMMs

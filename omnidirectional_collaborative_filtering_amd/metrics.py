@@ -80,6 +80,30 @@ def nMAE(y_true, y_pred, rating_range=1.0):
     return from_stats("nMAE", sse, sae, cnt, rs, *np.shape(y_true), rating_range)
 
 
+def ranking_from_rows(hits, dcg, n_relevant, k):
+    """Ranking metrics of top-k lists from the per-row statistics the merge kernel writes (ocf.h ocf_topk
+    row_rank; Model.evaluate_ranking), over the rows that have a relevant column at all:
+
+      hit_rate@k  mean of [hits > 0]
+      recall@k    mean of hits / n_relevant
+      ndcg@k      mean of dcg / sum_{j < min(n_relevant, k)} 1 / log2(j + 2)     (binary relevance)
+    'rows' is the number of such rows (0: the three means are nan).  Not compile(metrics=...) metrics."""
+    k = int(k)
+    hits = np.asarray(hits, np.float64).ravel()
+    dcg = np.asarray(dcg, np.float64).ravel()
+    nrel = np.asarray(n_relevant, np.float64).ravel()
+    keep = nrel > 0
+    rows = int(keep.sum())
+    names = ("hit_rate@%d" % k, "recall@%d" % k, "ndcg@%d" % k)
+    if rows == 0:
+        return {names[0]: float("nan"), names[1]: float("nan"), names[2]: float("nan"), "rows": 0}
+    hits, dcg, nrel = hits[keep], dcg[keep], nrel[keep]
+    ideal = np.concatenate([[0.0], np.cumsum(1.0 / np.log2(np.arange(k, dtype=np.float64) + 2.0))])
+    idcg = ideal[np.minimum(nrel, k).astype(np.int64)]
+    return {names[0]: float(np.mean(hits > 0)), names[1]: float(np.mean(hits / nrel)),
+            names[2]: float(np.mean(dcg / idcg)), "rows": rows}
+
+
 def compute_full_RMSE(sse_total, ratings_count):
     """train.py:243-252: sqrt(sum over test batches of SSE / sum of target_count)."""
     return float(np.sqrt(sse_total / ratings_count))

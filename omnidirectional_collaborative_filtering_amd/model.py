@@ -268,6 +268,72 @@ class Model(object):
         e.predict_dense(om, out)
         return out
 
+    # ------------------------------------------------------------------ recommendations (engine.Engine.topk)
+    # The k best columns of every batch row straight from the decoder GEMM (ocf.h ocf_topk): no [B, N] score
+    # matrix is written, the scores are bit-identical to predict's with an all-ones output mask, ordered by
+    # descending score and, for equal scores, ascending column; rows with fewer than k eligible columns end in
+    # (-1, -inf).  The lists run along the batch row, whatever the model's orientation.  Like predict, the three
+    # methods are collective under data parallelism with ZeRO-1 (the fp32 masters are all-gathered first): every
+    # rank must call them together.  Nothing of the training state changes (no stats row, no optimizer step).
+    def recommend_on_batch(self, x, k=10, exclude=None):
+        """x: dense inputs in predict's order.  exclude: [B, N] array or tensor, nonzero = never recommended.
+        Returns (items [B, k] int32, scores [B, k] fp32) as CUDA tensors."""
+        e = self.engine
+        blocks, _ = self._split_inputs(x)
+        zeros = torch.zeros(e.B, e.N, device=e.dev)
+        e.load_dense(blocks, zeros, zeros)
+        e.forward(training=False)
+        if exclude is not None:
+            ex = exclude if torch.is_tensor(exclude) else torch.as_tensor(np.asarray(exclude, np.float32))
+            if tuple(ex.shape) != (e.B, e.N):
+                raise ValueError("exclude has shape %s, expected (%d, %d)" % (tuple(ex.shape), e.B, e.N))
+            exclude = ex.to(e.dev, torch.float32).contiguous()
+        return e.topk(k, exclude=exclude)
+
+    def _rank_batch(self, gen, k, exclude_seen, relevance_min=None, relevance=False):
+        """next batch of the generator -> (rows, Engine.topk's result)"""
+        e = self.engine
+        self._check_gen(gen)
+        bi = gen.next_batch_index()
+        if bi is None:
+            raise StopIteration("generator exhausted (data_reader.py:418 yields None)")
+        self._load(None, gen, bi)
+        e.forward(training=False)
+        rows_ptr = gen.rows_dev.data_ptr() + 4 * bi * gen.B
+        ex = rel = None
+        if exclude_seen:
+            t = gen.src1.tiles(e.N)
+            ex = dict(ex_rows=rows_ptr, ex_rp=gen.src1.rp, ex_tptr=t["t_tptr"], ex_col=t["t_col"],
+                      ex_ntiles=t["t_ntiles"])
+        if relevance:
+            t = gen.src2.tiles(e.N)
+            rel = dict(rel_rows=rows_ptr, rel_rp=gen.src2.rp, rel_col=t["t_col"], rel_val=t["t_val"],
+                       rel_min=relevance_min)
+        return gen.rows_dev.view(-1)[bi * gen.B:(bi + 1) * gen.B], e.topk(k, exclude=ex, relevance=rel)
+
+    def recommend_generator(self, generator, steps, k=10, exclude_seen=True):
+        """BatchGenerator batches of any split (the generator advances as under evaluate_generator).
+        exclude_seen: the batch rows' input entries (every entry of the split's input CSR) are never recommended.
+        Returns (rows [steps * B] int64 dataset row indices, items [steps * B, k] int32, scores [steps * B, k])."""
+        if not isinstance(generator, BatchGenerator):
+            raise ValueError("recommend_generator takes a data_reader.data_gen generator (dense batches: "
+                             "recommend_on_batch)")
+        out = [self._rank_batch(generator, k, exclude_seen) for _ in range(int(steps))]
+        return (torch.cat([r for r, _ in out]).to(torch.int64), torch.cat([t[0] for _, t in out]),
+                torch.cat([t[1] for _, t in out]))
+
+    def evaluate_ranking(self, generator, steps, k=10, relevance_min=None):
+        """Hit rate, recall and NDCG at k of a valid / test generator: the inputs are the split's input ratings,
+        seen items are excluded, and the relevant items of a row are its held-out entries with a rating >=
+        relevance_min (None: every held-out entry).  The per-row counts come from the merge kernel; returns
+        metrics.ranking_from_rows of them: {"hit_rate@k", "recall@k", "ndcg@k", "rows"}."""
+        if not isinstance(generator, BatchGenerator) or generator.split == "train":
+            raise ValueError("evaluate_ranking needs a valid or test generator (a train generator has no held-out "
+                             "entries)")
+        rr = torch.cat([self._rank_batch(generator, k, True, relevance_min, True)[1][2] for _ in range(int(steps))])
+        rr = rr.cpu().numpy()
+        return M.ranking_from_rows(rr[:, 0], rr[:, 1], rr[:, 2], k)
+
     def fit(self, x, y, batch_size=None, epochs=1, verbose=1, callbacks=None, validation_split=0.0, shuffle=True,
             **kw):
         """Keras 2.0.4 Model.fit on dense arrays (train_jester.py:78-79): the last validation_split fraction
