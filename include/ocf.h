@@ -361,6 +361,10 @@ int ocf_gemm(const OcfGemmArgs* args, void* stream);
  * running top-k per batch row against its k-th value, writes one candidate list per (row, group)), then the
  * merge kernel (a wave per batch row merges the groups' lists; optionally scores the list against held-out
  * entries).  No grid barrier, no wait between workgroups.
+ * The transposed call (bias_by_row, h_dtype1, h_blocked at the end of the struct) ranks along the other axis: M =
+ * the output columns with the decoder weight as h (fp32 master, row-major or 64x64-blocked shadow), N = the
+ * catalogue rows with their hidden codes as W, score[m][n] = h[m] . W[n] + bias[m].  M may be several hundred
+ * thousand rows: every product of M, groups, k and the leading dimensions is taken in 64 bits.
  */
 #define OCF_TOPK_MAX_K 128
 typedef struct OcfTopkArgs {
@@ -396,6 +400,15 @@ typedef struct OcfTopkArgs {
   const int32_t* rel_rows; const int64_t* rel_rp; const int32_t* rel_col; const float* rel_val;
   float rel_min;
   float* row_rank;          /* [m_real][4]; required with rel_rows                                          */
+  /* the transposed call (all zero = the call as described above).  The score is symmetric in its two factors, so
+   * the k best catalogue rows of every output column come from the same two launches with the operands exchanged:
+   * h = the decoder weight [M = columns][ldh], W = a table of hidden codes [N = catalogue rows][ldw] in the
+   * compute dtype, bias along M, exclusion / relevance CSRs transposed (RatingsCSR.transposed).  Any field set
+   * selects kernel variants of their own; the variants of the plain call are not touched. */
+  int bias_by_row;          /* score[m][n] = h[m] . W[n] + bias[m], bias [M] (the same fp32 acc + b)        */
+  int h_dtype1;             /* 0: h is in the compute dtype; else OCF_DT_* + 1 of h: fp32 (rounded to the
+                               compute dtype while staging, as W is for w_dtype = F32) or the compute dtype  */
+  int h_blocked;            /* the 16-bit h is stored 64x64-blocked (ldh % 64 == 0), as w_blocked for W     */
 } OcfTopkArgs;
 /* bytes of OcfTopkArgs.work for these arguments (host only, no device access); -1 + ocf_last_error on bad ones */
 int64_t ocf_topk_workspace(const OcfTopkArgs* args);

@@ -142,6 +142,7 @@ class OcfTopkArgs(ctypes.Structure):
         ("ex_mask", P), ("ld_ex", I64), ("ex_mrows", P),
         ("out_idx", P), ("out_val", P), ("ld_out", I64), ("work", P), ("work_bytes", I64),
         ("rel_rows", P), ("rel_rp", P), ("rel_col", P), ("rel_val", P), ("rel_min", F32), ("row_rank", P),
+        ("bias_by_row", I32), ("h_dtype1", I32), ("h_blocked", I32),      # the transposed call (0 = as before)
     ]
 
 

@@ -13,6 +13,9 @@
 // Launch 2, topk_merge_kernel: a wave per batch row stages the groups' lists in LDS, drops what lies below the
 // largest minimum of a full list (k candidates are at least that good), selects k times the best of the rest and,
 // given held-out entries, counts hits / DCG / relevant columns of the final list.
+// The transposed call (OcfTopkArgs bias_by_row / h_dtype1 / h_blocked) ranks along the other axis with the same two
+// launches: the decoder weight rows as the M operand (fp32 master, row-major or 64x64-blocked shadow), a table of
+// hidden codes as the N operand, the bias along M.  It has select variants of its own (TR = true).
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -38,6 +41,7 @@ struct SelParams {
   const int32_t* ex_rows; const int64_t* ex_rp; const int32_t* ex_tptr; const int32_t* ex_col; int ex_ntiles;
   const float* ex_mask; int64_t ld_ex; const int64_t* ex_mrows;
   uint2* cand;              // [M][groups][k]: (score bits, column), unordered; (-inf, -1) = empty
+  int h_blk, bias_m;        // TR variants only: h stored 64x64-blocked; bias indexed by M row
 };
 
 // LDS row stride (floats) of the per-row score lists: k rounded up to 16 plus one 16-B slot (an odd number of
@@ -46,7 +50,11 @@ inline int list_stride(int k) { return ((k + 15) & ~15) + 4; }
 
 __host__ __device__ __forceinline__ uint2 none_entry() { return make_uint2(0xFF800000u, 0xFFFFFFFFu); }   // (-inf, -1)
 
-template <typename CT, typename WGT>
+// AGT: the M operand's element type in memory (CT, or float = the fp32 master rounded while staging, as WGT is
+// on the N side).  TR: the transposed call's variants -- the M operand may be 64x64-blocked (p.h_blk) and the bias
+// may run along M (p.bias_m; the tile's 128 values sit in LDS behind the lists).  With AGT = CT and TR = false
+// every line below compiles to what it was before these parameters existed.
+template <typename CT, typename WGT, typename AGT = CT, bool TR = false>
 __global__ void __launch_bounds__(GT_THREADS) topk_select_kernel(SelParams p) {
   using Cfg = GemmCfg<CT, false, false, CT, WGT>;
   constexpr int BK = Cfg::BK;
@@ -106,10 +114,18 @@ __global__ void __launch_bounds__(GT_THREADS) topk_select_kernel(SelParams p) {
     mslot = ms;
   };
 
-  const CT* Ag = reinterpret_cast<const CT*>(p.h);
+  const AGT* Ag = reinterpret_cast<const AGT*>(p.h);
   const WGT* Bg = reinterpret_cast<const WGT*>(p.W);
   const bool bblk = sizeof(WGT) == 2 && p.w_blk;
-  const __amdgpu_buffer_rsrc_t ra = tile_rsrc(Ag + (int64_t)m0 * p.ldh);
+  const bool ablk = TR && sizeof(AGT) == 2 && p.h_blk;
+  const __amdgpu_buffer_rsrc_t ra =
+      ablk ? tile_rsrc(reinterpret_cast<const char*>(Ag) + Stager<AGT, CT, GT_BM, false>::blocked_origin(p.ldh, m0, 0))
+           : tile_rsrc(Ag + (int64_t)m0 * p.ldh);
+  const bool bias_m = TR && p.bias_m;
+  float* brow = lists + GT_BM * p.ks;                               // [128] the tile's biases (TR, bias by M row)
+  if constexpr (TR) {
+    if (tid < GT_BM) brow[tid] = bias_m ? p.bias[m0 + tid] : 0.f;   // read from step 1 on, after the K-loop's barriers
+  }
   const int nk = p.K / BK;
   char* buf0 = lds;
   char* buf1 = lds + Cfg::BUF;
@@ -128,10 +144,10 @@ __global__ void __launch_bounds__(GT_THREADS) topk_select_kernel(SelParams p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
     {
-      Stager<CT, CT, GT_BM, false> sa;
+      Stager<AGT, CT, GT_BM, false> sa;
       Stager<WGT, CT, GT_BN, false> sb;
-      const uint32_t sta = decltype(sa)::step_bytes(p.ldh, false), stb = decltype(sb)::step_bytes(p.ldw, bblk);
-      sa.load(ra, p.ldh, 0, tid, false);
+      const uint32_t sta = decltype(sa)::step_bytes(p.ldh, ablk), stb = decltype(sb)::step_bytes(p.ldw, bblk);
+      sa.load(ra, p.ldh, 0, tid, false, ablk);
       sb.load(rb, p.ldw, 0, tid, false, bblk);
       sa.store(buf0, tid);
       sb.store(buf0 + Cfg::ImgA::BYTES, tid);
@@ -139,7 +155,7 @@ __global__ void __launch_bounds__(GT_THREADS) topk_select_kernel(SelParams p) {
       for (int kt = 0; kt < nk; ++kt) {
         const bool more = kt + 1 < nk;
         if (more) {
-          sa.load(ra, p.ldh, (kt + 1) * sta, tid, false);
+          sa.load(ra, p.ldh, (kt + 1) * sta, tid, false, ablk);
           sb.load(rb, p.ldw, (kt + 1) * stb, tid, false, bblk);
         }
         const char* cb = (kt & 1) ? buf1 : buf0;
@@ -156,13 +172,24 @@ __global__ void __launch_bounds__(GT_THREADS) topk_select_kernel(SelParams p) {
 #pragma unroll
     for (int bj = 0; bj < 2; ++bj) {
       const int n = n0 + wn + acc_col(bj, lane);
-      const float bias = p.bias[n];
       const bool pad = n >= p.n_real;
+      if constexpr (TR) {
+        const float bias_n = bias_m ? 0.f : p.bias[n];
 #pragma unroll
-      for (int bi = 0; bi < 2; ++bi)
+        for (int bi = 0; bi < 2; ++bi)
 #pragma unroll
-        for (int r = 0; r < 16; ++r)
-          Y[(wm + acc_row(bi, r, lane)) * YS + wn + acc_col(bj, lane)] = pad ? NEG_INF : acc[bi][bj][r] + bias;
+          for (int r = 0; r < 16; ++r) {
+            const int row = wm + acc_row(bi, r, lane);
+            Y[row * YS + wn + acc_col(bj, lane)] = pad ? NEG_INF : acc[bi][bj][r] + (bias_m ? brow[row] : bias_n);
+          }
+      } else {
+        const float bias = p.bias[n];
+#pragma unroll
+        for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            Y[(wm + acc_row(bi, r, lane)) * YS + wn + acc_col(bj, lane)] = pad ? NEG_INF : acc[bi][bj][r] + bias;
+      }
     }
     __syncthreads();
     // ---- 2. exclusions of this tile
@@ -368,14 +395,24 @@ void check_shape(const OcfTopkArgs& a) {
   OCF_CHECK(a.groups >= 0, "ocf_topk: groups >= 0 (0 = the library's choice)");
 }
 
-template <typename CT, typename WGT>
+template <typename CT, typename WGT, typename AGT = CT, bool TR = false>
 void launch_select(const SelParams& p, int gm, hipStream_t s) {
   using Cfg = GemmCfg<CT, false, false, CT, WGT>;
-  const int lds = Cfg::OPER_LDS + GT_BM * 8 + GT_THREADS * 8 + GT_BM * p.ks * 4;
-  OCF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&topk_select_kernel<CT, WGT>),
+  const int lds = Cfg::OPER_LDS + GT_BM * 8 + GT_THREADS * 8 + GT_BM * p.ks * 4 + (TR ? GT_BM * 4 : 0);
+  OCF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&topk_select_kernel<CT, WGT, AGT, TR>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  hipLaunchKernelGGL((topk_select_kernel<CT, WGT>), dim3(gm * p.groups), dim3(GT_THREADS), lds, s, p);
+  hipLaunchKernelGGL((topk_select_kernel<CT, WGT, AGT, TR>), dim3(gm * p.groups), dim3(GT_THREADS), lds, s, p);
   OCF_HIP(hipGetLastError());
+}
+
+// the transposed call's variants: the N side as before, the M side in the compute dtype or fp32
+template <typename CT>
+void launch_select_tr(const SelParams& p, int gm, bool w32, bool h32, hipStream_t s) {
+  if (w32) {
+    if (h32) launch_select<CT, float, float, true>(p, gm, s); else launch_select<CT, float, CT, true>(p, gm, s);
+  } else {
+    if (h32) launch_select<CT, CT, float, true>(p, gm, s); else launch_select<CT, CT, CT, true>(p, gm, s);
+  }
 }
 
 }  // namespace
@@ -397,6 +434,7 @@ extern "C" int ocf_topk(const OcfTopkArgs* args, void* stream) {
   const OcfTopkArgs& a = *args;
   check_shape(a);
   OCF_CHECK(a.ld_out >= a.k, "ocf_topk: ld_out < k");
+  OCF_CHECK(!a.bias_by_row || a.bias, "ocf_topk: bias_by_row needs a bias of M values (null bias)");
   OCF_CHECK(a.h && a.W && a.bias && a.out_idx && a.out_val, "ocf_topk: null h, W, bias, out_idx or out_val");
   OCF_CHECK(!(a.ex_rows && a.ex_mask), "ocf_topk: both exclusion forms given (row-segment and dense)");
   OCF_CHECK(!a.ex_rows || (a.ex_rp && a.ex_tptr && a.ex_col && a.ex_ntiles * GT_BN >= a.N),
@@ -407,6 +445,11 @@ extern "C" int ocf_topk(const OcfTopkArgs* args, void* stream) {
   OCF_CHECK(a.w_dtype == OCF_F32 || a.w_dtype == a.compute_dtype, "ocf_topk: W must be fp32 or the compute dtype");
   OCF_CHECK(!a.w_blocked || a.w_dtype != OCF_F32, "ocf_topk: the blocked flag needs a 16-bit weight (w_dtype f16 / bf16)");
   OCF_CHECK(!a.w_blocked || a.ldw % 64 == 0, "ocf_topk: blocked W needs ldw % 64 == 0");
+  OCF_CHECK(a.h_dtype1 == 0 || a.h_dtype1 == OCF_F32 + 1 || a.h_dtype1 == a.compute_dtype + 1,
+            "ocf_topk: h must be fp32 or the compute dtype (h_dtype1 = 0, or OCF_DT_* + 1)");
+  const bool h32 = a.h_dtype1 ? a.h_dtype1 == OCF_F32 + 1 : a.compute_dtype == OCF_F32;
+  OCF_CHECK(!a.h_blocked || !h32, "ocf_topk: a blocked h needs a 16-bit operand (h in fp32 is row-major)");
+  OCF_CHECK(!a.h_blocked || a.ldh % 64 == 0, "ocf_topk: blocked h needs ldh % 64 == 0");
   OCF_CHECK(a.ldh % 8 == 0 && a.ldw % 8 == 0 && a.ldh >= a.K && a.ldw >= a.K,
             "ocf_topk: ldh and ldw must be multiples of 8 and >= K");
   OCF_CHECK(!a.rel_rows || a.row_rank, "ocf_topk: relevance given without row_rank");
@@ -423,9 +466,16 @@ extern "C" int ocf_topk(const OcfTopkArgs* args, void* stream) {
   p.ex_rows = a.ex_rows; p.ex_rp = a.ex_rp; p.ex_tptr = a.ex_tptr; p.ex_col = a.ex_col; p.ex_ntiles = a.ex_ntiles;
   p.ex_mask = a.ex_mask; p.ld_ex = a.ld_ex; p.ex_mrows = a.ex_mrows;
   p.cand = reinterpret_cast<uint2*>(reinterpret_cast<char*>(a.work) + WORK_HEADER);
+  p.h_blk = a.h_blocked != 0; p.bias_m = a.bias_by_row != 0;
   const int gm = a.M / GT_BM;
   const bool w32 = a.w_dtype == OCF_F32;
-  switch (a.compute_dtype) {
+  if (a.bias_by_row || a.h_dtype1 || a.h_blocked) {      // any new field set: the transposed call's variants
+    switch (a.compute_dtype) {
+      case OCF_F16: launch_select_tr<_Float16>(p, gm, w32, h32, s); break;
+      case OCF_BF16: launch_select_tr<__bf16>(p, gm, w32, h32, s); break;
+      default: launch_select<float, float, float, true>(p, gm, s);
+    }
+  } else switch (a.compute_dtype) {
     case OCF_F16:
       if (w32) launch_select<_Float16, float>(p, gm, s); else launch_select<_Float16, _Float16>(p, gm, s);
       break;

@@ -143,6 +143,30 @@ class data_reader(object):
                          for k in ("train", "valid_in", "valid_tgt", "test_in", "test_tgt")}
         return self._dev
 
+    def catalogue(self, split):
+        """FixedSplit.catalogue(split) with its CSRs on the device, built once per split: dict(keys, n, inputs,
+        none, seen, held).  inputs carries one empty row behind the candidate rows (index n: what the padding rows
+        of the last encode batch read), none is an all-empty target CSR of the same shape; seen / held are the
+        transposed exclusion and relevance CSRs (their .tiles(R_p) are built on first use)."""
+        cats = self.__dict__.setdefault("_catalogues", {})
+        if split not in cats:
+            from .dataset import RatingsCSR
+            keys, inputs, seen, held = self.data.catalogue(split)
+            n = len(keys)
+            padded = RatingsCSR(np.concatenate([inputs.row_ptr, inputs.row_ptr[-1:]]), inputs.col, inputs.val,
+                                list(keys), inputs.dup)
+            none = RatingsCSR(np.zeros(n + 2, np.int64), np.zeros(0, np.int32), np.zeros(0, np.float32), list(keys))
+            d = self.device
+            cats[split] = dict(keys=keys, n=n, inputs=_DeviceCSR(padded, d), none=_DeviceCSR(none, d),
+                               seen=_DeviceCSR(seen, d), held=None if held is None else _DeviceCSR(held, d))
+        return cats[split]
+
+    def catalogue_gen(self, batch_size, split, auxilliary_mask_type=None, aux_var_value=-1):
+        """the candidate rows of catalogue(split), in order, as eval batches (Engine.encode_rows)"""
+        if auxilliary_mask_type not in AUX_FEED:
+            raise ValueError("Auxilliary mask type %r doesn't exist" % (auxilliary_mask_type,))
+        return CatalogueGenerator(self, int(batch_size), split, auxilliary_mask_type, float(aux_var_value))
+
     def split_for_validation(self, val_split, seed=None):
         raise NotImplementedError("ablation eval mode is out of scope")
 
@@ -231,16 +255,19 @@ class BatchGenerator(object):
         np.random.set_state((st[0], np.frombuffer(a.key, dtype=np.uint32).copy(), int(a.pos), st[3], st[4]))
         return keep
 
+    def _sources(self):
+        """(input CSR, target CSR or None) of the split, on the device"""
+        dev = self.r._on_device()
+        if self.split == "train":
+            return dev["train"], None
+        if self.split == "valid":
+            return dev["valid_in"], dev["valid_tgt"]
+        return dev["test_in"], dev["test_tgt"]
+
     def _start(self):
         self.started = True
         r = self.r
-        dev = r._on_device()
-        if self.split == "train":
-            self.src1, self.src2 = dev["train"], None
-        elif self.split == "valid":
-            self.src1, self.src2 = dev["valid_in"], dev["valid_tgt"]
-        else:
-            self.src1, self.src2 = dev["test_in"], dev["test_tgt"]
+        self.src1, self.src2 = self._sources()
         rows, boff, self.tcount = self.plan(self.src1.rng_lens, None if self.src2 is None else self.src2.rng_lens)
         nb = self.num_batches
         self.rows_host = rows
@@ -625,3 +652,38 @@ class BatchGenerator(object):
         return inputs, t
 
     next = __next__   # py2-style gen.next() as used at train.py:233
+
+
+class CatalogueGenerator(BatchGenerator):
+    """The candidate rows of data_reader.catalogue(split) in their order, unshuffled, as eval-mode batches whose
+    targets are empty: ceil(n / B) batches, the last one filled up with an empty row -- so the scatter, the
+    aux-mask feeds and the row-gather tables are BatchGenerator's, unchanged.  Draws nothing from NumPy's RNG."""
+
+    def __init__(self, reader, B, split, aux_type, aux):
+        self.cat = reader.catalogue(split)
+        self.r = reader
+        self.B = B
+        self.sparsity = [1.0, 1.0]
+        self.split = "catalogue/" + split          # not "train": eval mode (source 1 = inputs only)
+        self.shuffle = False
+        self.aux_type = aux_type
+        self.aux = aux
+        self.return_count = False
+        self.pass_through = False
+        self.keys = self.cat["keys"]
+        self.n = self.cat["n"]
+        self.num_batches = -(-self.n // B)
+        self.i = 0
+        self.started = False
+        self.dp_shard = None
+        self.seed = 0
+
+    def _sources(self):
+        return self.cat["inputs"], self.cat["none"]
+
+    def plan(self, row_lengths1, row_lengths2=None):
+        nb, B = self.num_batches, self.B
+        rows = np.minimum(np.arange(nb * B, dtype=np.int64), self.n).reshape(nb, B)     # row n: the empty one
+        boff = np.zeros((nb, B + 1), dtype=np.int64)
+        np.cumsum(row_lengths1[rows], axis=1, out=boff[:, 1:])
+        return rows, boff, row_lengths2[rows].sum(axis=1)

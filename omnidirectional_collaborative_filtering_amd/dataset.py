@@ -111,6 +111,24 @@ class RatingsCSR:
         np.cumsum(counts.reshape(self.n_rows, n_tiles), axis=1, out=tptr[:, 1:])
         return col_s, val_s, lidx_s, tptr
 
+    def transposed(self, n_cols):
+        """The same entries as a CSR of n_cols rows: row c holds the entries of column c, and an entry's column is
+        the position of the row it came from.  Every row is sorted by ascending column (one stable_order pass over
+        the source columns: the source rows are already ascending), duplicates are kept, in source order.  The
+        per-column view of a rating set: what every column has seen, or holds out (FixedSplit.catalogue)."""
+        n_cols = int(n_cols)
+        if self.nnz and (int(self.col.max()) >= n_cols or int(self.col.min()) < 0):
+            raise ValueError("transposed: a column index lies outside [0, %d)" % n_cols)
+        if self.n_rows >= 2 ** 31:
+            raise ValueError("transposed: %d rows do not fit an int32 column index" % self.n_rows)
+        rows = np.repeat(np.arange(self.n_rows, dtype=np.int32), self.row_lengths())
+        order = stable_order(self.col.astype(np.int64)) if self.nnz else np.zeros(0, np.int64)
+        rp = np.zeros(n_cols + 1, dtype=np.int64)
+        np.cumsum(np.bincount(self.col, minlength=n_cols), out=rp[1:])
+        c = RatingsCSR(rp, rows[order], self.val[order], list(range(n_cols)))
+        c.dup = None if self.dup is None else dup_chain(rp, c.col)     # no duplicates there, none here
+        return c
+
     def column_shard(self, c0, c1):
         """entries with c0 <= col < c1, columns re-based to 0, list order and full-row positions kept"""
         lens = self.row_lengths()
@@ -183,6 +201,16 @@ def lookup_col(col_index, cid):
         return col_index[str(cid)]
 
 
+def _positions(keys, pos, n):
+    """out[pos[k]] = i for the i-th of keys that pos knows; -1 elsewhere (length n)"""
+    out = np.full(n, -1, dtype=np.int64)
+    for i, k in enumerate(keys):
+        p = pos.get(k)
+        if p is not None:
+            out[p] = i
+    return out
+
+
 @dataclass
 class FixedSplit:
     """eval_mode='fixed_split' data (data_reader.py:57-80)."""
@@ -199,6 +227,70 @@ class FixedSplit:
         return FixedSplit(c1 - c0, *(getattr(self, k).column_shard(c0, c1)
                                      for k in ("train", "valid_in", "valid_tgt", "test_in", "test_tgt")),
                           col_ids=list(self.col_ids[c0:c1]))
+
+    def catalogue(self, split):
+        """The candidate rows of a per-column ranking (Model.recommend_columns / evaluate_ranking_columns): every
+        row a column could be recommended, what each is encoded from, and the two per-column views of the split.
+
+        Returns (keys, inputs, seen_by_col, held_by_col):
+        keys         'train' / 'valid': the keys of train, in its order; 'test': those, then the valid_tgt keys not
+                     among them.
+        inputs       RatingsCSR [len(keys) x num_cols], the ratings candidate row i is encoded from.  'train' /
+                     'valid': its train row.  'test': its test_in row verbatim where the key has one (so its code
+                     is the one a test generator's batch row gets), otherwise its train entries followed by its
+                     valid_tgt entries.
+        seen_by_col  inputs.transposed(num_cols): per column, the candidate rows it has rated (never recommended).
+        held_by_col  the held-out entries (valid_tgt / test_tgt) transposed, rows as positions in keys; None for
+                     'train'."""
+        if split not in ("train", "valid", "test"):
+            raise ValueError("catalogue: split must be 'train', 'valid' or 'test', not %r" % (split,))
+        tr = self.train
+        keys = list(tr.keys)
+        pos = {k: i for i, k in enumerate(keys)}
+        if len(pos) != len(keys):
+            raise ValueError("catalogue: the train keys are not unique")
+        if split != "test":
+            inputs = RatingsCSR(tr.row_ptr, tr.col, tr.val, keys, tr.dup)
+            tgt = None if split == "train" else self.valid_tgt
+        else:
+            va, ti = self.valid_tgt, self.test_in
+            for k in va.keys:
+                if k not in pos:
+                    pos[k] = len(keys)
+                    keys.append(k)
+            R = len(keys)
+            row_of = lambda csr: _positions(csr.keys, pos, R)     # catalogue position -> row of csr, or -1
+            in_tr, in_va, in_ti = row_of(tr), row_of(va), row_of(ti)
+            # up to two segments per candidate row out of the pool train | valid_tgt | test_in
+            base_va, base_ti = tr.nnz, tr.nnz + va.nnz
+            start = np.zeros((R, 2), np.int64)
+            lens = np.zeros((R, 2), np.int64)
+            has_ti = in_ti >= 0
+            for j, (csr, rows, base, use) in enumerate(((tr, in_tr, 0, ~has_ti), (va, in_va, base_va, ~has_ti))):
+                ok = use & (rows >= 0)
+                start[ok, j] = base + csr.row_ptr[rows[ok]]
+                lens[ok, j] = csr.row_ptr[rows[ok] + 1] - csr.row_ptr[rows[ok]]
+            start[has_ti, 0] = base_ti + ti.row_ptr[in_ti[has_ti]]
+            lens[has_ti, 0] = ti.row_ptr[in_ti[has_ti] + 1] - ti.row_ptr[in_ti[has_ti]]
+            fl, fs = lens.reshape(-1), start.reshape(-1)
+            take = np.repeat(fs - (np.cumsum(fl) - fl), fl) + np.arange(int(fl.sum()), dtype=np.int64)
+            rp = np.zeros(R + 1, dtype=np.int64)
+            np.cumsum(lens.sum(axis=1), out=rp[1:])
+            inputs = RatingsCSR(rp, np.concatenate([tr.col, va.col, ti.col])[take],
+                                np.concatenate([tr.val, va.val, ti.val])[take], list(keys))
+            inputs.dup = dup_chain(rp, inputs.col)
+            tgt = self.test_tgt
+        seen_by_col = inputs.transposed(self.num_cols)
+        held_by_col = None
+        if tgt is not None:
+            at = np.fromiter((pos.get(k, -1) for k in tgt.keys), dtype=np.int64, count=len(tgt.keys))
+            if (at < 0).any():
+                raise ValueError("catalogue: %d held-out rows of the %s split are not among the candidate rows"
+                                 % (int((at < 0).sum()), split))
+            held = RatingsCSR.from_coo(np.repeat(at, tgt.row_lengths()), tgt.col, tgt.val, len(keys), keys=keys,
+                                       dup_free=tgt.dup is None)
+            held_by_col = held.transposed(self.num_cols)
+        return keys, inputs, seen_by_col, held_by_col
 
     def save(self, path):
         arrs = {"num_cols": np.array(self.num_cols), "col_ids": np.asarray([str(c) for c in self.col_ids])}

@@ -1222,6 +1222,134 @@ class Engine:
         del keep
         return (idx, val) if rank is None else (idx, val, rank)
 
+    # ---------------------------------------------------------------- per-column top-K (the transposed ocf_topk)
+    def encode_rows(self, gen):
+        """The last hidden activations of every row of a catalogue generator (data_reader.catalogue_gen: the
+        candidate rows in order, unshuffled, the last batch filled up with empty rows): the eval-mode forward over
+        all gen.n rows in batches of B, h[L-1][:B] of batch i copied to rows i*B .. of a table [R_p, Hp_last] in the
+        compute dtype, R_p = gen.n rounded up to 128; rows >= gen.n are zero.  Returns the table.  Nothing of the
+        training state changes (no stats row, no step count, dropout off)."""
+        if self.comm is not None:
+            raise ValueError("encode_rows: a feature-parallel engine holds a column shard of the inputs; the "
+                             "per-column ranking is not built for it")
+        if gen.B != self.B:
+            raise ValueError("encode_rows: generator batch_size %d != engine batch_size %d" % (gen.B, self.B))
+        L = len(self.H)
+        R, B = int(gen.n), self.B
+        codes = torch.zeros(ru(max(R, 1), TILE), self.Hp[L - 1], device=self.dev, dtype=self.tdt)
+        while True:
+            bi = gen.next_batch_index()
+            if bi is None:
+                break
+            self.load_batch(gen.scatter_args(bi, engine_args=self.scatter_args()), gen.targets(bi, self.N),
+                            gather=gen.gather_tables(bi))
+            self.forward(training=False)
+            self._finish_deferred_encoder()
+            r0 = bi * B
+            n = min(B, R - r0)
+            if n > 0:
+                codes[r0:r0 + n].copy_(self.h[L - 1][:n])
+        return codes
+
+    def topk_columns(self, codes, n_codes, k, columns=None, exclude=None, relevance=None, groups=None, out=None,
+                     master=False):
+        """The k best catalogue rows of every output column: ocf_topk with the operands exchanged (the score
+        h_i . W_out[u] + b_out[u] is symmetric in its factors), so no [rows, N] score array exists anywhere.
+        codes: encode_rows' table [R_p, Hp_last] (compute dtype), n_codes its real rows.  The M side is the decoder
+        operand itself -- the 16-bit shadow (row-major or 64x64-blocked) when there is one, else the fp32 master;
+        master=True reads the fp32 master in any case (rounded while staging: the same bits) -- no copy.
+        columns: None = every column, lists in column order; or int64 column indices [C] (their weight rows and
+        biases are gathered from the master into a temporary operand).
+        Returns idx [C, k] int32 positions into the catalogue (-1 past the eligible ones), val [C, k] fp32 (-inf
+        there), in descending score, equal scores by ascending position[, row_rank [C, 4]].
+
+        exclude: None; a device fp32 [C, >= n_codes] tensor (nonzero = excluded); or dict(ex_rp, ex_tptr, ex_col,
+        ex_ntiles), the tile index over R_p columns of a CSR with one row per output column (the transposed input
+        CSR, data_reader.catalogue(split)["seen"].tiles(R_p)): column u excludes every entry of its row.
+        relevance: dict(rel_rp, rel_col, rel_val[, rel_min]) of such a CSR (the transposed held-out entries).
+        groups, out: as in topk.  Nothing of the training state changes."""
+        if self.comm is not None:
+            raise ValueError("topk_columns: a feature-parallel engine holds a column shard; its lists would be "
+                             "those of its own columns only, which is not built")
+        k, n_codes = int(k), int(n_codes)
+        if self.master_sync is not None:
+            self.master_sync()
+        L = len(self.H)
+        Hp = self.Hp[L - 1]
+        if not (torch.is_tensor(codes) and codes.is_cuda and codes.dtype == self.tdt and codes.dim() == 2
+                and codes.shape[1] == Hp and codes.stride(1) == 1 and codes.shape[0] % TILE == 0
+                and 0 <= n_codes <= codes.shape[0]):
+            raise ValueError("topk_columns: codes = encode_rows' table, a device %s tensor [multiple of 128, %d] "
+                             "holding n_codes rows" % (self.tdt, Hp))
+        a = _lib.OcfTopkArgs()
+        a.compute_dtype = self.cdt
+        a.bias_by_row = 1
+        if columns is None:
+            (Wt, wdt), blk = ((self.W[L], _lib.DT_F32), 0) if master else (self._wop(L), self._wblk(L))
+            bias, C, Mp = self.b[L], self.N, self.Np
+            ids = getattr(self, "_col_ids", None)
+            if ids is None:
+                ids = self._col_ids = torch.arange(self.Np, device=self.dev, dtype=torch.int32)
+        else:
+            cols = torch.as_tensor(columns, device=self.dev).to(torch.int64).view(-1)
+            C = cols.numel()
+            if C == 0 or int(cols.min()) < 0 or int(cols.max()) >= self.N:
+                raise ValueError("topk_columns: columns = indices in [0, %d), at least one" % self.N)
+            Mp = ru(C, TILE)
+            Wt = torch.zeros(Mp, Hp, device=self.dev, dtype=torch.float32)
+            Wt[:C] = self.W[L].index_select(0, cols)
+            bias = torch.zeros(Mp, device=self.dev, dtype=torch.float32)
+            bias[:C] = self.b[L].index_select(0, cols)
+            wdt, blk, ids = _lib.DT_F32, 0, cols.to(torch.int32)
+        a.h, a.ldh, a.h_dtype1, a.h_blocked = ptr(Wt), Wt.shape[1], wdt + 1, blk
+        a.W, a.w_dtype, a.ldw, a.w_blocked = ptr(codes), self.cdt, codes.stride(0), 0
+        a.bias = ptr(bias)
+        a.M, a.N, a.K, a.m_real, a.n_real = Mp, codes.shape[0], Hp, C, n_codes
+        a.k, a.groups = k, int(groups or 0)
+        keep = [exclude, relevance, Wt, bias, ids]
+        if torch.is_tensor(exclude):
+            m = exclude
+            if not (m.is_cuda and m.dtype == torch.float32 and m.dim() == 2 and m.shape[0] >= C
+                    and m.shape[1] >= n_codes and m.stride(1) == 1):
+                raise ValueError("topk_columns: the dense exclusion is a device fp32 [>= %d, >= %d] tensor"
+                                 % (C, n_codes))
+            a.ex_mask, a.ld_ex = ptr(m), m.stride(0)
+        elif exclude is not None:
+            a.ex_rows = ptr(ids)
+            a.ex_rp, a.ex_tptr, a.ex_col = [v.data_ptr() if torch.is_tensor(v) else v
+                                            for v in (exclude["ex_rp"], exclude["ex_tptr"], exclude["ex_col"])]
+            a.ex_ntiles = int(exclude["ex_ntiles"])
+        if out is not None:
+            idx, val = out
+            for t, dt in ((idx, torch.int32), (val, torch.float32)):
+                if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.dim() == 2 and t.shape[0] >= C
+                        and t.shape[1] >= k and t.stride(1) == 1 and t.stride(0) == idx.stride(0)):
+                    raise ValueError("topk_columns: out = (int32, fp32) device tensors [>= %d, >= %d] with one row "
+                                     "stride" % (C, k))
+        else:
+            idx = torch.empty(C, k, device=self.dev, dtype=torch.int32)
+            val = torch.empty(C, k, device=self.dev, dtype=torch.float32)
+        a.out_idx, a.out_val, a.ld_out = ptr(idx), ptr(val), idx.stride(0)
+        rank = None
+        if relevance is not None:
+            a.rel_rows = ptr(ids)
+            a.rel_rp, a.rel_col, a.rel_val = [v.data_ptr() if torch.is_tensor(v) else v
+                                              for v in (relevance["rel_rp"], relevance["rel_col"], relevance["rel_val"])]
+            rm = relevance.get("rel_min")
+            a.rel_min = float("-inf") if rm is None else float(rm)
+            rank = torch.empty(C, 4, device=self.dev, dtype=torch.float32)
+            a.row_rank = ptr(rank)
+        nb = int(_lib.load().ocf_topk_workspace(ctypes.byref(a)))
+        if nb < 0:
+            raise _lib.OcfError("ocf_topk_workspace failed: %s" % _lib.load().ocf_last_error().decode())
+        w = getattr(self, "_topk_work", None)
+        if w is None or w.numel() < nb:
+            w = self._topk_work = torch.empty(nb, device=self.dev, dtype=torch.uint8)
+        a.work, a.work_bytes = ptr(w), w.numel()
+        call("ocf_topk", a, cur_stream())
+        del keep
+        return (idx, val) if rank is None else (idx, val, rank)
+
     # ---------------------------------------------------------------- backward + update
     def backward_update(self, grads_out=None):
         """Backward pass; with grads_out=None the optimizer is fused into the weight-gradient GEMMs

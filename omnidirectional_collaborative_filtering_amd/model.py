@@ -334,6 +334,66 @@ class Model(object):
         rr = rr.cpu().numpy()
         return M.ranking_from_rows(rr[:, 0], rr[:, 1], rr[:, 2], k)
 
+    # ------------------------------------------------------------------ per-column recommendations
+    # The lists above run along the batch row.  For an item-row model (I-AutoRec: rows = items, columns = users)
+    # the question is the other one: the k best rows for every column.  The score h_i . W_out[u] + b_out[u] is
+    # symmetric in its factors, so every candidate row is encoded once (encode_rows: a table of hidden codes, R x H)
+    # and the same select / merge kernels run with the operands exchanged (Engine.topk_columns): the decoder weight
+    # rows on the M side, the codes on the N side, exclusion and relevance from the transposed CSRs
+    # (dataset.FixedSplit.catalogue).  No [R, N] score array exists anywhere.  Like predict, the three methods are
+    # collective under data parallelism with ZeRO-1 (the fp32 masters are all-gathered first): every rank must call
+    # them together.  Nothing of the training state changes, and nothing is drawn from NumPy's RNG.
+    def _encode_catalogue(self, reader, split, auxilliary_mask_type, aux_var_value):
+        gen = reader.catalogue_gen(self.engine.B, split, auxilliary_mask_type, aux_var_value)
+        self._check_gen(gen)
+        return gen.cat, self.engine.encode_rows(gen)
+
+    def encode_rows(self, reader, split="valid", auxilliary_mask_type=None, aux_var_value=-1):
+        """The embedding (last hidden activations, eval mode) of every candidate row of reader's catalogue for
+        `split` (dataset.FixedSplit.catalogue: 'train' / 'valid' = the train rows encoded from their train ratings;
+        'test' = those plus the rows first seen in validation, encoded from their test inputs).  The causal /
+        dropout mask feeds mark the row's input entries.  Returns (keys, codes): the row keys and a CUDA tensor
+        [R, H] in the compute dtype.  Collective under ZeRO-1 data parallelism, like predict."""
+        cat, codes = self._encode_catalogue(reader, split, auxilliary_mask_type, aux_var_value)
+        return cat["keys"], codes[:cat["n"], :self.engine.H[-1]]
+
+    def recommend_columns(self, reader, split="valid", k=10, exclude_seen=True, columns=None,
+                          auxilliary_mask_type=None, aux_var_value=-1):
+        """The k best candidate rows for every column (for an item-row model: k items for every user).
+        exclude_seen: the rows a column has an input rating for are never recommended to it.  columns: None = every
+        column, or a list of column indices.  Returns (keys, items [C, k] int32 positions into keys, -1 past the
+        eligible rows, scores [C, k] fp32) -- CUDA tensors, descending score, equal scores by ascending position.
+        Collective under ZeRO-1 data parallelism, like predict."""
+        cat, codes = self._encode_catalogue(reader, split, auxilliary_mask_type, aux_var_value)
+        ex = None
+        if exclude_seen:
+            t = cat["seen"].tiles(codes.shape[0])
+            ex = dict(ex_rp=cat["seen"].rp, ex_tptr=t["t_tptr"], ex_col=t["t_col"], ex_ntiles=t["t_ntiles"])
+        items, scores = self.engine.topk_columns(codes, cat["n"], k, columns=columns, exclude=ex)
+        return cat["keys"], items, scores
+
+    def evaluate_ranking_columns(self, reader, split="valid", k=10, relevance_min=None, auxilliary_mask_type=None,
+                                 aux_var_value=-1):
+        """Hit rate, recall and NDCG at k per column (per user, for an item-row model), as the literature reports
+        them: every column ranks the candidate rows it has not rated in the split's inputs, and its relevant rows
+        are its held-out entries (valid / test targets) with a rating >= relevance_min (None: all of them).
+        Returns metrics.ranking_from_rows of the per-column counts: {"hit_rate@k", "recall@k", "ndcg@k", "rows"},
+        rows = the columns with a relevant row.  Collective under ZeRO-1 data parallelism, like predict."""
+        if split not in ("valid", "test"):
+            raise ValueError("evaluate_ranking_columns needs split='valid' or 'test' (the train split has no "
+                             "held-out entries)")
+        cat, codes = self._encode_catalogue(reader, split, auxilliary_mask_type, aux_var_value)
+        rr = self._rank_columns(cat, codes, k, relevance_min)[2].cpu().numpy()
+        return M.ranking_from_rows(rr[:, 0], rr[:, 1], rr[:, 2], k)
+
+    def _rank_columns(self, cat, codes, k, relevance_min, columns=None):
+        """Engine.topk_columns with the catalogue's seen rows excluded and its held-out entries as relevance"""
+        seen, held = cat["seen"], cat["held"]
+        t, h = seen.tiles(codes.shape[0]), held.tiles(codes.shape[0])
+        ex = dict(ex_rp=seen.rp, ex_tptr=t["t_tptr"], ex_col=t["t_col"], ex_ntiles=t["t_ntiles"])
+        rel = dict(rel_rp=held.rp, rel_col=h["t_col"], rel_val=h["t_val"], rel_min=relevance_min)
+        return self.engine.topk_columns(codes, cat["n"], k, columns=columns, exclude=ex, relevance=rel)
+
     def fit(self, x, y, batch_size=None, epochs=1, verbose=1, callbacks=None, validation_split=0.0, shuffle=True,
             **kw):
         """Keras 2.0.4 Model.fit on dense arrays (train_jester.py:78-79): the last validation_split fraction
