@@ -43,7 +43,17 @@ class Optimizer:
 
 
 class SGD(Optimizer):
+    """p -= lr*g   (Keras 2.0.4 SGD.get_updates with momentum = 0, nesterov = False).
+
+    Keras' SGD also has momentum and Nesterov momentum; this library implements neither, so asking for
+    one raises instead of training silently without it."""
     kind = _lib.OPT_SGD
+
+    def __init__(self, lr=0.01, momentum=0.0, decay=0.0, nesterov=False):
+        if float(momentum) != 0.0 or nesterov:
+            raise ValueError("SGD: momentum / nesterov are not implemented (got momentum=%r, nesterov=%r)"
+                             % (momentum, nesterov))
+        super().__init__(lr, decay)
 
 
 class Adagrad(Optimizer):

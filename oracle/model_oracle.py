@@ -13,6 +13,7 @@ equations for exactly the graph model.py builds:
   train.py:50-51   Adagrad(lr, epsilon, decay=0)     Keras 2.0.4 Adagrad.get_updates
   train_jester.py:61 'rmsprop' (lr 1e-3, rho 0.9, eps 1e-8)  Keras 2.0.4 RMSprop.get_updates
   north_star       Adam (lr 1e-3, b1 .9, b2 .999, eps 1e-8)   Keras 2.0.4 Adam.get_updates
+  optimizers.SGD   plain SGD (momentum 0, no Nesterov)        Keras 2.0.4 SGD.get_updates
   train.py:102-121 mae / accurate_MAE / nMAE / accurate_RMSE / accurate_MSE
   train.py:243-255 compute_full_RMSE
 Weights use Keras' (in, out) layout; glorot_uniform init U(+-sqrt(6/(fan_in+fan_out))), zero bias.
@@ -235,6 +236,21 @@ class OmniOracle:
 
 
 # ---- optimizers (Keras 2.0.4 get_updates; accumulators start at 0) ------------------
+class SGDOracle:
+    """Keras 2.0.4 SGD.get_updates without momentum (momentum = 0, nesterov = False): p -= lr_t * g."""
+
+    def __init__(self, lr=0.01, decay=0.0):
+        self.lr, self.decay = lr, decay
+        self.iterations = 0
+
+    def step(self, params, grads):
+        lr = self.lr
+        if self.decay > 0:
+            lr = lr * (1.0 / (1.0 + self.decay * self.iterations))
+        self.iterations += 1
+        return [p - lr * g for p, g in zip(params, grads)]
+
+
 class AdagradOracle:
     def __init__(self, lr=0.01, epsilon=1e-8, decay=0.0):
         self.lr, self.eps, self.decay = lr, epsilon, decay

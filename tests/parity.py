@@ -21,7 +21,7 @@ import os
 import numpy as np
 
 from oracle.batch_oracle import scatter_rows_numpy
-from oracle.model_oracle import AdagradOracle, AdamOracle, OmniOracle, RMSpropOracle  # noqa: F401
+from oracle.model_oracle import AdagradOracle, AdamOracle, OmniOracle, RMSpropOracle, SGDOracle  # noqa: F401
 
 FP32_ABS = 1e-5
 UNIT_ROUNDOFF = {"float16": 2.0 ** -11, "bfloat16": 2.0 ** -8, "float32": 2.0 ** -24}
@@ -42,13 +42,14 @@ def dense(csr, rows, N, aux):
 def oracle_opt(name, lr=None):
     return {"adagrad": lambda: AdagradOracle(lr=lr or 0.005, epsilon=1e-8),
             "rmsprop": lambda: RMSpropOracle(lr=lr or 0.001),
-            "adam": lambda: AdamOracle(lr=lr or 0.001)}[name]()
+            "adam": lambda: AdamOracle(lr=lr or 0.001),
+            "sgd": lambda: SGDOracle(lr=lr or 0.05)}[name]()
 
 
 def our_opt(name, lr=None):
     from omnidirectional_collaborative_filtering_amd import optimizers as O
     return {"adagrad": lambda: O.Adagrad(lr=lr or 0.005, epsilon=1e-8), "rmsprop": lambda: O.RMSprop(lr=lr or 0.001),
-            "adam": lambda: O.Adam(lr=lr or 0.001)}[name]()
+            "adam": lambda: O.Adam(lr=lr or 0.001), "sgd": lambda: O.SGD(lr=lr or 0.05)}[name]()
 
 
 class Result:
@@ -180,7 +181,7 @@ def run_parity(compute_dtype, opt_name, layers, act, steps=4, B=128, H=100, aux_
         rmse_o = float(np.sqrt(sse_o / cnt_o))
     return Result(loss_g=float(np.mean(gpu_losses)), loss_o=float(np.mean(losses)), step_losses_g=gpu_losses,
                   step_losses_o=losses, rmse_g=rmse_g, rmse_o=rmse_o, w=w_gpu, ora=ora, env=env, om=om, gen=gen,
-                  live_rows_used=live_rows_used,
+                  live_rows_used=live_rows_used, w0=w0,
                   reader=rd, masks=masks, lr=opt.lr)
 
 

@@ -1,4 +1,7 @@
-"""MFMA GEMM core (ocf_gemm) vs a torch fp32 reference of the same op, every layout / dtype."""
+"""MFMA GEMM core (ocf_gemm): the raw products of the EPI_SLAB (with split-K) and EPI_GRAD epilogues against a
+torch fp64 product of the same rounded operands, in the three operand layouts and compute dtypes; the 64x64-blocked
+weight operand (bit-identical to row-major); the rounding and layout of EPI_OPTIM's 16-bit shadow.  The values of
+the other epilogues (BIAS_ACT, GRAD_ACT, PREDICT, MASKED_MSE, OPTIM) are checked in tests/test_epilogues_gpu.py."""
 import numpy as np
 import pytest
 import torch

@@ -32,6 +32,19 @@ def test_fp32_parity_operand_paths(gpu, gather, sparse_dw):
     assert_fp32(run_parity("float32", "adagrad", 1, "sigmoid", gather=gather, sparse_dw=sparse_dw))
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("gather,sparse_dw,l2", [(False, None, None), (True, False, None), (True, True, None),
+                                                 (False, None, 1e-2)])
+def test_fp32_parity_sgd(gpu, gather, sparse_dw, l2):
+    """SGD (no slots: s1 == NULL in every kernel it reaches) over the same three operand paths, and once with
+    l2; lr = 0.05 so four steps move the weights well above the 1e-5 bar"""
+    res = run_parity("float32", "sgd", 1, "sigmoid", gather=gather, sparse_dw=sparse_dw, lr=0.05, l2=l2)
+    moved = max(float(abs(wg - w0).max()) for wg, w0 in zip(res.w, res.w0))
+    print("largest weight change over the run: %.3e" % moved)
+    assert moved > 1e-4, moved               # ten times the bar: an update that did nothing would not pass
+    assert_fp32(res)
+
+
 # ---- dropout on (the benchmarked configuration: train.py:40,52; model.py:72-73) -------------------
 @pytest.mark.gpu
 @pytest.mark.parametrize("gather,sparse_dw", [(False, None), (True, False), (True, True)])
