@@ -37,6 +37,26 @@ extern "C" {
 #define OCF_OPTK_RMSPROP 2
 #define OCF_OPTK_ADAM 3
 
+/* training losses: rho applied to the residual e = m * y - t of every live target entry (rho(0) = 0, so the Keras
+ * mean over all B * N elements is a sum over the live entries).  loss_param: Huber's delta (> 0), ignored by the
+ * others.
+ *   OCF_LOSS_MSE      rho = e^2                                   rho' = 2 e      (train.py:49; the default)
+ *   OCF_LOSS_MAE      rho = |e|                                   rho' = sign(e), 0 at e = 0
+ *   OCF_LOSS_HUBER    rho = e^2 / 2 (|e| <= d), d (|e| - d / 2)   rho' = clamp(e, -d, d)
+ *   OCF_LOSS_LOGCOSH  rho = log cosh e                            rho' = tanh e
+ * Every kernel that takes a loss (OcfGatherArgs, OcfGemmArgs with OCF_EPI_MASKED_MSE, OcfMlpStepArgs,
+ * ocf_masked_loss) writes the delta it hands to the backward pass as
+ *   MSE: delta = e * m   with the caller's gscale = 2 / (B N)     (the factor 2 of rho' is folded into gscale)
+ *   else delta = rho'(e) * m   with the caller's gscale = 1 / (B N)
+ * and still produces SSE, SAE, count_nonzero(T + yhat) and the per-row SSE.  With a loss other than MSE the
+ * fourth float of every stats partial (chunk_stats, the per-row stats rows, stats_part; 0 / unwritten under MSE)
+ * carries the sum of rho(e); ocf_loss_sum adds the partials up.  A zero-initialised loss / loss_param is MSE:
+ * the same kernel instances and bits as before the fields existed. */
+#define OCF_LOSS_MSE 0
+#define OCF_LOSS_MAE 1
+#define OCF_LOSS_HUBER 2
+#define OCF_LOSS_LOGCOSH 3
+
 /* GEMM epilogues (ocf_gemm) */
 #define OCF_EPI_SLAB 0       /* split-K fp32 partial slabs                                   */
 #define OCF_EPI_BIAS_ACT 1   /* + bias, activation, dropout  (model.py:64-73)                */
@@ -44,7 +64,7 @@ extern "C" {
 #define OCF_EPI_GRAD 3       /* raw weight gradient (data-parallel path)                     */
 #define OCF_EPI_OPTIM 4      /* fused optimizer update of the weight tile (train.py:50-51)  */
 #define OCF_EPI_PREDICT 5    /* y = mask * (acc + b)   (model.py:82-86)                       */
-#define OCF_EPI_MASKED_MSE 6 /* masked MSE loss/grad on bucketed targets (train.py:49)       */
+#define OCF_EPI_MASKED_MSE 6 /* masked loss/grad on the targets (train.py:49 MSE; OcfGemmArgs loss) */
 
 /* Keras 2.0.4 optimizer scalars for one step (host computes lr incl. decay / Adam lr_t). */
 typedef struct OcfOptParams {
@@ -153,7 +173,7 @@ typedef struct OcfGatherArgs {
   const void* h; int h_dtype;                 /* [Bp][H] hidden activations (compute dtype)       */
   const float* bias; float aux;               /* output bias, output-mask value (train.py:47)     */
   float* delta_e;            /* per batch-local entry delta err*m (nullable)                      */
-  float* chunk_stats;        /* [n_chunks][4]: SSE, SAE, count_nonzero(T + yhat), 0               */
+  float* chunk_stats;        /* [n_chunks][4]: SSE, SAE, count_nonzero(T + yhat), 0 (see loss)    */
   void* d_out; int d_dtype; int64_t ld_d;     /* optional dense delta (zero elsewhere)            */
   /* decoder, optional (enc_part != NULL, one hidden layer): the hidden layer's bias / activation /
    * dropout applied here instead of by ocf_rows_reduce(OCF_REDUCE_BIAS_ACT) -- h[b] = dropout(act(the
@@ -171,6 +191,11 @@ typedef struct OcfGatherArgs {
    * last chunk of a row resets it); rows without chunks (padding, no targets) get the zero delta.  jr->part
    * and jr->chunk_stats must be this launch's part and chunk_stats, jr->H its H. */
   const struct OcfRowsReduceArgs* jr; uint32_t* row_arrive;
+  /* decoder: the loss (OCF_LOSS_*, 0 = MSE) and its parameter.  Not MSE: chunk_stats[c][3] = the chunk's sum of
+   * rho(e); the folded row reduction (jr) writes the row's sum to jr->stats_part[b][3]; a separate ocf_rows_reduce
+   * needs its stats4 set; the reduction as a job of a weight-gradient launch (OcfGemmArgs jr) and ocf_rank_step
+   * are MSE only */
+  int loss; float loss_param;
 } OcfGatherArgs;
 
 int ocf_gather_encoder(const OcfGatherArgs* args, void* stream);
@@ -233,6 +258,8 @@ typedef struct OcfRowsReduceArgs {
   void* h_out; int h_dtype; int n_real;
   float* db_part; float gscale;             /* GRAD_ACT: [Bp][H] bias-gradient rows * gscale     */
   const float* chunk_stats; float* stats_part; float* row_sse;   /* decoder stats -> per row      */
+  int stats4;                /* 1: stats_part[b][3] = the row's sum of chunk_stats[c][3] (a loss other than MSE:
+                              * the sum of rho(e)); 0: stats_part[b][3] = 0                          */
 } OcfRowsReduceArgs;
 
 int ocf_rows_reduce(const OcfRowsReduceArgs* args, void* stream);
@@ -345,6 +372,9 @@ typedef struct OcfGemmArgs {
    * at row dn_rows[b] (nullable: b) of [*][ld_dn], columns < n_real; an entry wherever t != 0 or m != 0.
    * Replaces the bucket pass of ocf_dense_targets for dense batches (Model.fit / train_on_batch). */
   const float* dn_t; const float* dn_m; int64_t ld_dn; const int64_t* dn_rows;
+  /* MASKED_MSE: the loss (OCF_LOSS_*, 0 = MSE) and its parameter, in all three target modes.  Not MSE: the delta
+   * is rho'(e) * m (opt.gscale = 1 / (B N)) and stats_part[tile][3] = the tile's sum of rho(e) */
+  int loss; float loss_param;
 } OcfGemmArgs;
 
 int ocf_gemm(const OcfGemmArgs* args, void* stream);
@@ -563,6 +593,11 @@ int ocf_sumsq(const float* x, int64_t n, float scale, float* ws, float* out, voi
 /* reduce OCF_EPI_MASKED_MSE partials to out[4 + M] = {sse, sae, nnz(T+yhat), 0, row_sse[M]}. */
 int ocf_stats_finalize(const float* stats_part, int n_parts, const float* row_sse_part, int n_tiles, int M,
                        float* out, void* stream);
+/* ocf_loss_sum -- out[0] = the sum of stats_part[i][3] over i < n_parts in a fixed order: the step's sum of rho(e)
+ * from the stats partials of a loss other than MSE (the per-row stats rows of the row gathers, OCF_EPI_MASKED_MSE's
+ * stats_part).  The logged loss is out[0] / (B N).  Issue it after ocf_stats_finalize when out is slot 3 of that
+ * call's output (which it zeroes). */
+int ocf_loss_sum(const float* stats_part, int n_parts, float* out, void* stream);
 
 /* ocf_sparse_tiles -- bucket a batch's sparse A operand (the OcfGemmArgs sp_* descriptor) by
  * (M tile t < gm, K-step kt < nk): bucket t*nk + kt holds, for the batch rows b in [64 kt, 64 kt + 64)
@@ -681,7 +716,7 @@ int ocf_mt_host_jump(const uint32_t* key_in, int64_t n_blocks, uint32_t* key_out
 
 /*
  * Model ABI: one omni_model (/root/reference/model.py:43-99) trained by five calls per step,
- *   ocf_forward -> ocf_masked_mse -> ocf_backward -> ocf_opt_step (per parameter)
+ *   ocf_forward -> ocf_masked_mse (or ocf_masked_loss) -> ocf_backward -> ocf_opt_step (per parameter)
  * the Keras train_on_batch that fit_generator runs (train.py:157) split at the points a binding drives:
  * forward (model.py:64-86), the masked MSE and its per-row sums (train.py:49, 102-121), the backward pass to
  * raw fp32 gradients, and the elementwise Keras update (train.py:50-51).  Parameters and gradients are
@@ -726,6 +761,16 @@ int ocf_forward(OcfCtx* ctx, const float* const* inputs, int64_t ld_in, int B, i
  * divided by gscale = 2 / (B N) -- kept unscaled so 16-bit operands do not underflow. */
 int ocf_masked_mse(const float* pred, const float* T, const float* out_mask, int64_t ld, int B, int N,
                    float* out_grad, int64_t ld_grad, float* out_stats, void* stream);
+/* ocf_masked_loss -- ocf_masked_mse for any OCF_LOSS_* (loss_param: Huber's delta > 0): e = pred - T,
+ * out_grad = rho'(e) * out_mask (MSE: e * out_mask, the bits of ocf_masked_mse), the gradient with respect to the
+ * unmasked output divided by the gscale the caller then passes to ocf_backward: 2 / (B N) for OCF_LOSS_MSE,
+ * 1 / (B N) for the others.  out_stats (4 + 4 B floats): {sum e^2, sum |e|, count_nonzero(T + pred), loss = sum
+ * rho(e) / (B N)}, the per-row sums e^2 [B], |e| [B], count_nonzero [B] as ocf_masked_mse writes them, then the
+ * per-row sums of rho(e) [B] at out_stats[4 + 3 B ..] (their total is slot 3 times B N).  log cosh is evaluated as
+ * |e| + log1p(exp(-2 |e|)) - ln 2 (its even Taylor polynomial below |e| = 0.5, where that form cancels) and tanh
+ * as -expm1(-2 |e|) / (expm1(-2 |e|) + 2) with e's sign: finite for every finite e. */
+int ocf_masked_loss(int loss, float loss_param, const float* pred, const float* T, const float* out_mask, int64_t ld,
+                    int B, int N, float* out_grad, int64_t ld_grad, float* out_stats, void* stream);
 /* ocf_backward -- the gradients of the last ocf_forward (same B) from out_grad: gW[i] / gb[i] (shapes of
  * W[i] / b[i]) = gscale * the backward pass of model.py:64-86 (dropout masks of that forward). */
 int ocf_backward(OcfCtx* ctx, const float* grad, int64_t ld_grad, int B, float gscale, float* const* gW,
@@ -776,6 +821,9 @@ typedef struct OcfMlpStepArgs {
    * + n), as the layer-wise path draws it; mask[i] (u8 [Bp][hidden_p[i]], required when keep < 1) receives it. */
   float keep; uint64_t seed, stream;
   uint8_t* mask[OCF_MAX_HIDDEN];
+  /* the loss (OCF_LOSS_*, 0 = MSE) and its parameter.  Not MSE: opt.gscale = 1 / (B N) and stats[3] = the sum of
+   * rho(e) (0 under MSE) */
+  int loss; float loss_param;
 } OcfMlpStepArgs;
 int64_t ocf_mlp_step_workspace(const OcfMlpStepArgs* args);
 int ocf_mlp_step(const OcfMlpStepArgs* args, void* stream);

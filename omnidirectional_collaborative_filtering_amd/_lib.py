@@ -17,6 +17,7 @@ ACT = {"linear": 0, None: 0, "sigmoid": 1, "tanh": 2, "relu": 3}
 OPT_SGD, OPT_ADAGRAD, OPT_RMSPROP, OPT_ADAM = 0, 1, 2, 3
 LIVE_REC = 144                 # ocf.h OCF_LIVE_REC
 EPI_SLAB, EPI_BIAS_ACT, EPI_GRAD_ACT, EPI_GRAD, EPI_OPTIM, EPI_PREDICT, EPI_MASKED_MSE = range(7)
+LOSS_MSE, LOSS_MAE, LOSS_HUBER, LOSS_LOGCOSH = range(4)     # ocf.h OCF_LOSS_*
 
 P = ctypes.c_void_p
 I32 = ctypes.c_int
@@ -87,6 +88,7 @@ class OcfGatherArgs(ctypes.Structure):
         ("enc_part", P), ("enc_cptr", P), ("bias_h", P), ("act", I32), ("keep", F32), ("seed", U64), ("stream", U64),
         ("a_out", P), ("mask_out", P), ("m_real", I32), ("n_real", I32), ("zero_word", P),
         ("jr", P), ("row_arrive", P),
+        ("loss", I32), ("loss_param", F32),
     ]
 
 
@@ -99,6 +101,7 @@ class OcfRowsReduceArgs(ctypes.Structure):
         ("bias", P), ("act", I32), ("keep", F32), ("seed", U64), ("stream", U64),
         ("mask_in", P), ("mask_out", P), ("a_out", P), ("a_in", P), ("h_out", P), ("h_dtype", I32), ("n_real", I32),
         ("db_part", P), ("gscale", F32), ("chunk_stats", P), ("stats_part", P), ("row_sse", P),
+        ("stats4", I32),
     ]
 
 
@@ -127,6 +130,7 @@ class OcfGemmArgs(ctypes.Structure):
         ("js_sp", P), ("js_rs", P), ("js_out", P), ("js_nparts", I32), ("js_ntiles", I32), ("js_M", I32),
         ("row_live", P), ("sp_rowptr", P), ("sp_rowent", P), ("jr", P), ("sp_nent", I64),
         ("dn_t", P), ("dn_m", P), ("ld_dn", I64), ("dn_rows", P),
+        ("loss", I32), ("loss_param", F32),
     ]
 
 
@@ -200,7 +204,8 @@ class OcfMlpStepArgs(ctypes.Structure):
                 ("sW2", P * _L), ("sb1", P * _L), ("sb2", P * _L), ("shadow", P * _L), ("shadow_blocked", I32),
                 ("act", I32), ("compute_dtype", I32), ("opt", OcfOptParams), ("stats", P), ("work", P),
                 ("work_bytes", I64), ("barrier", P), ("wgs", I32), ("trace", P), ("keep", ctypes.c_float),
-                ("seed", ctypes.c_uint64), ("stream", ctypes.c_uint64), ("mask", P * 8)]
+                ("seed", ctypes.c_uint64), ("stream", ctypes.c_uint64), ("mask", P * 8),
+                ("loss", I32), ("loss_param", ctypes.c_float)]
 
     def __init__(self, *a, **kw):
         super().__init__(*a, **kw)
@@ -264,6 +269,7 @@ SIGNATURES = {
     "ocf_opt_step_ex": (I32, [ctypes.POINTER(OcfOptStepArgs), P]),
     "ocf_bias_opt_from_partials": (I32, [P, P, I32, I64, I32, P, P, P, ctypes.POINTER(OcfOptParams), P]),
     "ocf_stats_finalize": (I32, [P, I32, P, I32, I32, P, P]),
+    "ocf_loss_sum": (I32, [P, I32, P, P]),
     "ocf_sumsq": (I32, [P, I64, F32, P, P, P]),
     "ocf_gather_encoder": (I32, [ctypes.POINTER(OcfGatherArgs), P]),
     "ocf_gather_decoder": (I32, [ctypes.POINTER(OcfGatherArgs), P]),
@@ -283,6 +289,7 @@ SIGNATURES = {
     "ocf_ctx_destroy": (I32, [P]),
     "ocf_forward": (I32, [P, P, I64, I32, I32, U64, P, I64, P, I64, P, P]),
     "ocf_masked_mse": (I32, [P, P, P, I64, I32, I32, P, I64, P, P]),
+    "ocf_masked_loss": (I32, [I32, F32, P, P, P, I64, I32, I32, P, I64, P, P]),
     "ocf_backward": (I32, [P, P, I64, I32, F32, P, P, P]),
     "ocf_set_tuning": (I32, [ctypes.c_char_p, I32, ctypes.POINTER(I32)]),
     "ocf_check_async": (I32, []),

@@ -239,6 +239,22 @@ __global__ void __launch_bounds__(256) stats_finalize_kernel(const float* sp, in
   if (lane == 0) out[4 + m] = r;
 }
 
+// the step's sum of rho(e) (a loss other than MSE): the fourth float of the n_parts stats partials, summed as
+// stats_finalize_kernel's block 0 sums the other three (stride-256 partials, then the LDS tree)
+__global__ void __launch_bounds__(256) loss_sum_kernel(const float* sp, int n_parts, float* out) {
+  __shared__ float red[256];
+  const int tid = threadIdx.x;
+  float a = 0.f;
+  for (int i = tid; i < n_parts; i += 256) a += sp[(int64_t)i * 4 + 3];
+  red[tid] = a;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  if (tid == 0) out[0] = red[0];
+}
+
 // sum of squares, two passes with a fixed order: 1,024 block partials (block b: elements b*256 + i,
 // strided by the grid, a fixed LDS tree), then one block adds them in order and accumulates
 // scale * sum into out[0] (the l2 penalty of Keras' W_regularizer, model.py:66,82)
@@ -386,6 +402,14 @@ extern "C" int ocf_bias_opt_from_partials(float* b, const float* db_part, int pa
   if (n == 0) return 0;
   hipLaunchKernelGGL(bias_opt_partials_kernel, dim3((n + 63) / 64), dim3(256), 0, (hipStream_t)stream, b, db_part,
                      parts, ld, n, s1, s2, g_out, *opt);
+  OCF_HIP(hipGetLastError());
+  OCF_TRY_END
+}
+
+extern "C" int ocf_loss_sum(const float* stats_part, int n_parts, float* out, void* stream) {
+  OCF_TRY_BEGIN
+  OCF_CHECK(stats_part && out && n_parts >= 0, "ocf_loss_sum: null pointer / n_parts");
+  hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, stats_part, n_parts, out);
   OCF_HIP(hipGetLastError());
   OCF_TRY_END
 }

@@ -2,6 +2,7 @@
 // wave (C layout of v_mfma_f32_32x32x*: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)).
 #pragma once
 #include "ocf_gemm.h"
+#include "ocf_loss.h"
 
 namespace ocf {
 
@@ -363,46 +364,53 @@ struct EpiPredict {
 // The dense d tile (zero where no target) is written in the compute dtype for the backward
 // GEMMs, its column sums give the output-bias gradient, and SSE / SAE / count_nonzero(T+yhat)
 // / per-row SSE feed the loss and the train.py metrics.
-struct EpiMaskedMSE {
+// LOSS (ocf.h OCF_LOSS_*): for a loss rho other than MSE, d = rho'(err) * m (the caller's gscale is 1/(B*N)) and the
+// tile's sum of rho(err) goes to the stats partial's fourth float; the MSE instance is the code it was.
+// (one parameter block for every loss instance)
+struct MaskedLossParams {
+  const float* bias;        // output bias [N]
+  // bucket target mode (bk_ptr != nullptr): entries bucketed by 128-column tile
+  const int* bk_ptr;        // [n_tiles+1]
+  const int* bk_rc;         // (row << 7) | (col & 127)
+  const float* bk_t;        // target value
+  const float* bk_m;        // output-mask value
+  // row-segment target mode: each batch row's entries of this column tile, from the target
+  // CSR's column-sorted view; a thread owns a row (deterministic sums, no atomics)
+  const int32_t* t_rows;
+  const int64_t* t_rp;
+  const int32_t* t_tptr;
+  const int32_t* t_col;
+  const float* t_val;
+  const int32_t* t_lidx;
+  const uint8_t* t_flag;
+  const int64_t* t_lboff;
+  int t_ntiles;
+  float t_aux;
+  // dense target mode (dn_t != nullptr): targets / output masks as dense fp32 arrays, batch row b at row
+  // dn_rows[b] (or b) of [*][ld_dn]; an entry wherever t != 0 or m != 0 (Model.fit / train_on_batch)
+  const float* dn_t;
+  const float* dn_m;
+  int64_t ld_dn;
+  const int64_t* dn_rows;
+  int n_real;
+  void* d_out;              // dense delta [M][ld_d] compute dtype (nullable: eval)
+  int d_dtype;
+  int64_t ld_d;
+  float* db_part;           // [M/128][ld_db] column sums * gscale (nullable)
+  int64_t ld_db;
+  float gscale;
+  float* stats_part;        // [n_tiles * gm][4]: sse, sae, nnz(T+yhat), 0 (MSE) / the sum of rho(err)
+  float* row_sse_part;      // [n_tiles][M] (nullable)
+  int m_real;
+  float loss_param;         // Huber's delta (last: the members before it sit where the MSE-only struct had them)
+};
+template <int LOSS>
+struct EpiMaskedLoss {
   static constexpr int YS = GT_BN + 4;   // LDS row stride (floats) of the staged tile
   static constexpr int NPRE = 2;         // bucket entries per thread loaded in the prologue
-  static constexpr int LDS_NEED = GT_BM * YS * 4 + GT_BM * 4 * 4 + GT_BM * 4 + 4 * GT_BN * 4 + 3 * 4 * 4;
-  struct Params {
-    const float* bias;        // output bias [N]
-    // bucket target mode (bk_ptr != nullptr): entries bucketed by 128-column tile
-    const int* bk_ptr;        // [n_tiles+1]
-    const int* bk_rc;         // (row << 7) | (col & 127)
-    const float* bk_t;        // target value
-    const float* bk_m;        // output-mask value
-    // row-segment target mode: each batch row's entries of this column tile, from the target
-    // CSR's column-sorted view; a thread owns a row (deterministic sums, no atomics)
-    const int32_t* t_rows;
-    const int64_t* t_rp;
-    const int32_t* t_tptr;
-    const int32_t* t_col;
-    const float* t_val;
-    const int32_t* t_lidx;
-    const uint8_t* t_flag;
-    const int64_t* t_lboff;
-    int t_ntiles;
-    float t_aux;
-    // dense target mode (dn_t != nullptr): targets / output masks as dense fp32 arrays, batch row b at row
-    // dn_rows[b] (or b) of [*][ld_dn]; an entry wherever t != 0 or m != 0 (Model.fit / train_on_batch)
-    const float* dn_t;
-    const float* dn_m;
-    int64_t ld_dn;
-    const int64_t* dn_rows;
-    int n_real;
-    void* d_out;              // dense delta [M][ld_d] compute dtype (nullable: eval)
-    int d_dtype;
-    int64_t ld_d;
-    float* db_part;           // [M/128][ld_db] column sums * gscale (nullable)
-    int64_t ld_db;
-    float gscale;
-    float* stats_part;        // [n_tiles * gm][4]: sse, sae, nnz(T+yhat), unused
-    float* row_sse_part;      // [n_tiles][M] (nullable)
-    int m_real;
-  };
+  static constexpr int NS = LossStats<LOSS>::N;   // stats values per tile: sse, sae, count (+ the sum of rho)
+  static constexpr int LDS_NEED = GT_BM * YS * 4 + GT_BM * 4 * 4 + GT_BM * 4 + 4 * GT_BN * 4 + NS * 4 * 4;
+  using Params = MaskedLossParams;
   struct Pre {
     int b0, b1;               // bucket mode: bucket range
     int rc[NPRE];             // bucket mode: prefetched entries; segment mode: column | -1
@@ -452,14 +460,23 @@ struct EpiMaskedMSE {
     q.s_lo += NPRE;
     return q;
   }
+  // the delta of one entry, and its rho added to the running sum (MSE: err * m, nothing added)
+  __device__ static float delta(float err, float m, float lp, float& rho) {
+    if constexpr (LOSS == OCF_LOSS_MSE) {
+      return err * m;
+    } else {
+      rho += loss_value<LOSS>(err, lp);
+      return loss_grad<LOSS>(err, lp) * m;
+    }
+  }
   __device__ static void entry(float* Y, uint32_t* bits, float* rsse, int m0, int rc, float t, float m, float& sse,
-                               float& sae, float& cnt) {
+                               float& sae, float& cnt, float lp, float& rho) {
     int row = rc >> 7, nl = rc & 127;
     int ml = row - m0;
     if (rc < 0 || ml < 0 || ml >= GT_BM) return;
     float yhat = m * Y[ml * YS + nl];
     float err = yhat - t;
-    Y[ml * YS + nl] = err * m;
+    Y[ml * YS + nl] = delta(err, m, lp, rho);
     atomicOr(&bits[ml * 4 + (nl >> 5)], 1u << (nl & 31));
     sse += err * err;
     sae += fabsf(err);
@@ -472,7 +489,7 @@ struct EpiMaskedMSE {
     uint32_t* bits = reinterpret_cast<uint32_t*>(c.lds + GT_BM * YS * 4);
     float* rsse = reinterpret_cast<float*>(c.lds + GT_BM * YS * 4 + GT_BM * 16);
     float* colp = rsse + GT_BM;          // [4 waves][GT_BN]
-    float* red = colp + 4 * GT_BN;       // [3][4]
+    float* red = colp + 4 * GT_BN;       // [NS][4]
     // 1. stage y = acc + b
 #pragma unroll
     for (int bj = 0; bj < 2; ++bj) {
@@ -488,6 +505,9 @@ struct EpiMaskedMSE {
     __syncthreads();
     // 2. this tile's target entries
     float sse = 0.f, sae = 0.f, cnt = 0.f;
+    [[maybe_unused]] float rho = 0.f;
+    float lp = 0.f;                       // (MSE: never read)
+    if constexpr (LOSS != OCF_LOSS_MSE) lp = p.loss_param;
     if (p.dn_t) {
       // dense targets: thread tid owns row tid % 128 of the tile and its half (tid / 128) of the columns, so
       // its row-SSE share, the row's mask bits and every sum are its own (no atomics but the final
@@ -514,7 +534,7 @@ struct EpiMaskedMSE {
             const int nl = c0 + j0 + u;
             const float yhat = m[u] * Y[ml * YS + nl];
             const float err = yhat - t[u];
-            Y[ml * YS + nl] = err * m[u];
+            Y[ml * YS + nl] = delta(err, m[u], lp, rho);
             if (j0 + u < 32) w0 |= 1u << (j0 + u);
             else w1 |= 1u << (j0 + u - 32);
             rs += err * err;
@@ -529,9 +549,9 @@ struct EpiMaskedMSE {
       atomicAdd(&rsse[ml], rs);   // exactly two addends onto 0: order-independent
     } else if (p.bk_ptr) {
 #pragma unroll
-      for (int k = 0; k < NPRE; ++k) entry(Y, bits, rsse, c.m0, q.rc[k], q.t[k], q.m[k], sse, sae, cnt);
+      for (int k = 0; k < NPRE; ++k) entry(Y, bits, rsse, c.m0, q.rc[k], q.t[k], q.m[k], sse, sae, cnt, lp, rho);
       for (int e = q.b0 + c.tid + NPRE * GT_THREADS; e < q.b1; e += GT_THREADS)
-        entry(Y, bits, rsse, c.m0, p.bk_rc[e], p.bk_t[e], p.bk_m[e], sse, sae, cnt);
+        entry(Y, bits, rsse, c.m0, p.bk_rc[e], p.bk_t[e], p.bk_m[e], sse, sae, cnt, lp, rho);
     } else {
       // segment mode: live targets of this row half, at most one per (row, column)
       const int ml = c.tid & (GT_BM - 1);
@@ -541,7 +561,7 @@ struct EpiMaskedMSE {
         if (nl < 0) return;
         const float yhat = m * Y[ml * YS + nl];
         const float err = yhat - t;
-        Y[ml * YS + nl] = err * m;
+        Y[ml * YS + nl] = delta(err, m, lp, rho);
         atomicOr(&bits[ml * 4 + (nl >> 5)], 1u << (nl & 31));
         rs += err * err;
         sae += fabsf(err);
@@ -621,9 +641,12 @@ struct EpiMaskedMSE {
       sse += __shfl_xor(sse, off);
       sae += __shfl_xor(sae, off);
       cnt += __shfl_xor(cnt, off);
+      if constexpr (LOSS != OCF_LOSS_MSE) rho += __shfl_xor(rho, off);
     }
     const int wave = c.tid >> 6;
     if (c.lane == 0) { red[wave] = sse; red[4 + wave] = sae; red[8 + wave] = cnt; }
+    if constexpr (LOSS != OCF_LOSS_MSE)
+      if (c.lane == 0) red[12 + wave] = rho;
     __syncthreads();
     if (p.d_out && p.db_part && c.tid < GT_BN)
       p.db_part[(int64_t)c.tile_m * p.ld_db + c.n0 + c.tid] =
@@ -634,11 +657,13 @@ struct EpiMaskedMSE {
       sp[0] = (red[0] + red[1]) + (red[2] + red[3]);
       sp[1] = (red[4] + red[5]) + (red[6] + red[7]);
       sp[2] = (red[8] + red[9]) + (red[10] + red[11]);
-      sp[3] = 0.f;
+      if constexpr (LOSS == OCF_LOSS_MSE) sp[3] = 0.f;
+      else sp[3] = (red[12] + red[13]) + (red[14] + red[15]);
     }
     if (p.row_sse_part && c.tid < GT_BM)
       p.row_sse_part[(int64_t)c.tile_n * sh.M + c.m0 + c.tid] = rsse[c.tid];
   }
 };
+using EpiMaskedMSE = EpiMaskedLoss<OCF_LOSS_MSE>;
 
 }  // namespace ocf

@@ -141,7 +141,9 @@ void dispatch_epi(const OcfGemmArgs& g, hipStream_t s) {
       break;
     case OCF_EPI_MASKED_MSE:
       if constexpr (A_ROW) {
-        EpiMaskedMSE::Params p;
+        check_loss(g.loss, g.loss_param, "ocf_gemm MASKED_MSE");
+        MaskedLossParams p;
+        p.loss_param = g.loss_param;
         p.bias = g.bias; p.bk_ptr = g.bk_ptr; p.bk_rc = g.bk_rc; p.bk_t = g.bk_t; p.bk_m = g.bk_m;
         p.d_out = g.h_out; p.d_dtype = g.h_dtype; p.ld_d = g.ld_out; p.db_part = g.db_part; p.ld_db = g.ld_db;
         p.gscale = g.opt.gscale; p.stats_part = g.stats_part; p.row_sse_part = g.row_sse_part;
@@ -157,7 +159,12 @@ void dispatch_epi(const OcfGemmArgs& g, hipStream_t s) {
         OCF_CHECK(g.dn_t || g.bk_ptr || (g.t_rows && g.t_rp && g.t_tptr && g.t_col && g.t_val && g.t_lidx && g.t_flag &&
                                g.t_lboff && g.t_ntiles * GT_BN >= g.N),
                   "ocf_gemm MASKED_MSE: bucket or row-segment targets required");
-        launch<CT, ACOL, BCOL, WGT, EpiMaskedMSE>(g, p, s);
+        switch (g.loss) {
+          case OCF_LOSS_MAE: launch<CT, ACOL, BCOL, WGT, EpiMaskedLoss<OCF_LOSS_MAE>>(g, p, s); break;
+          case OCF_LOSS_HUBER: launch<CT, ACOL, BCOL, WGT, EpiMaskedLoss<OCF_LOSS_HUBER>>(g, p, s); break;
+          case OCF_LOSS_LOGCOSH: launch<CT, ACOL, BCOL, WGT, EpiMaskedLoss<OCF_LOSS_LOGCOSH>>(g, p, s); break;
+          default: launch<CT, ACOL, BCOL, WGT, EpiMaskedMSE>(g, p, s);
+        }
         return;
       }
       break;
@@ -380,6 +387,9 @@ extern "C" int ocf_train_step_rows(const OcfRowStepArgs* a, void* stream) {
   auto ev = [&](int k) {
     if (a->ev[k]) OCF_HIP(hipEventRecord((hipEvent_t)a->ev[k], s));
   };
+  // (the reduction as jobs of the dW_out launch sums three stats per chunk: no sum of rho)
+  OCF_CHECK(a->dec.loss == OCF_LOSS_MSE || a->jr_on != 1,
+            "ocf_train_step_rows: a loss other than OCF_LOSS_MSE needs the row reduction in the decoder (jr_on = 2)");
   OcfGatherArgs d = a->dec;
   d.jr = a->jr_on == 2 ? &a->jr : nullptr;      // the row reduction in the decoder (d.row_arrive) ...
   ev(0);

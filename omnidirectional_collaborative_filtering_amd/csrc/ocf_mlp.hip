@@ -54,6 +54,8 @@ struct P {
   float keep; uint64_t seed, stream; uint8_t* mask[MAXL];
   float* rowp;            // [Np / 32][Bp] per column-tile row sse
   float* totp;            // [tiles][waves][3] per output tile and wave sse / sae / count
+  float* rhop;            // [tiles][waves] (a loss other than MSE) per output tile and wave sum of rho(e)
+  float loss_param;       // Huber's delta
   uint32_t* bar; uint32_t* err; int max_polls;
   uint64_t* trace;
 };
@@ -440,7 +442,9 @@ __device__ __forceinline__ void epi_delta(const P& p, int i, const Frag<NE>& f, 
   }
 }
 
-template <typename CT, int KIND>
+// LOSS (ocf.h OCF_LOSS_*): delta_L = rho'(e) M and the sum of rho(e) in stats[3] for a loss other than MSE; the MSE
+// instance is the code it was
+template <typename CT, int KIND, int LOSS>
 __global__ void __launch_bounds__(THREADS) mlp_step_kernel(P p) {
   __shared__ __attribute__((aligned(16))) char lds[Geo<CT>::BYTES];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -485,6 +489,7 @@ __global__ void __launch_bounds__(THREADS) mlp_step_kernel(P p) {
       Frag<4> dl;
       dl.n = n;
       float sse = 0.f, sae = 0.f, cnt = 0.f, rs[4];
+      [[maybe_unused]] float rho = 0.f;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int m = v.m[j];
@@ -496,7 +501,12 @@ __global__ void __launch_bounds__(THREADS) mlp_step_kernel(P p) {
           sse += se;
           sae += fabsf(e);
           cnt += (ttv[j] + y != 0.f) ? 1.f : 0.f;
-          d = e * mkv[j];
+          if constexpr (LOSS == OCF_LOSS_MSE) {
+            d = e * mkv[j];
+          } else {
+            rho += loss_value<LOSS>(e, p.loss_param);
+            d = loss_grad<LOSS>(e, p.loss_param) * mkv[j];
+          }
         }
         pub(&p.d[L][(int64_t)m * p.Np + n], d);
         dl.m[j] = m;
@@ -514,7 +524,10 @@ __global__ void __launch_bounds__(THREADS) mlp_step_kernel(P p) {
         sse += __shfl_xor(sse, o, 64);
         sae += __shfl_xor(sae, o, 64);
         cnt += __shfl_xor(cnt, o, 64);
+        if constexpr (LOSS != OCF_LOSS_MSE) rho += __shfl_xor(rho, o, 64);
       }
+      if constexpr (LOSS != OCF_LOSS_MSE)
+        if (lane == 0) pub(&p.rhop[(int64_t)t * WAVES + wave], rho);
       if (lane == 0) {
         const int64_t slot = (int64_t)t * WAVES + wave;
         pub(&p.totp[slot * 3 + 0], sse);
@@ -563,14 +576,22 @@ __global__ void __launch_bounds__(THREADS) mlp_step_kernel(P p) {
         }
         for (int k = 0; k < 3; ++k)
           for (int o = 32; o > 0; o >>= 1) a[k] += __shfl_xor(a[k], o, 64);
+        [[maybe_unused]] float ar = 0.f;     // (a loss other than MSE) the slots' sums of rho, in a fixed order
+        if constexpr (LOSS != OCF_LOSS_MSE) {
+          for (int t = threadIdx.x; t < slots; t += THREADS) ar += ldc(p.rhop, t);
+          for (int o = 32; o > 0; o >>= 1) ar += __shfl_xor(ar, o, 64);
+        }
         float* ws = reinterpret_cast<float*>(lds + Geo<CT>::CS_OFF);
         __syncthreads();
         if (lane == 0)
           for (int k = 0; k < 3; ++k) ws[wave * 3 + k] = a[k];
+        if constexpr (LOSS != OCF_LOSS_MSE)
+          if (lane == 0) ws[3 * WAVES + wave] = ar;
         __syncthreads();
         if (threadIdx.x == 0) {
           for (int k = 0; k < 3; ++k) p.stats[k] = ((ws[k] + ws[3 + k]) + ws[6 + k]) + ws[9 + k];
-          p.stats[3] = 0.f;
+          if constexpr (LOSS == OCF_LOSS_MSE) p.stats[3] = 0.f;
+          else p.stats[3] = ((ws[12] + ws[13]) + ws[14]) + ws[15];
         }
         // per-row sums over the 32-column blocks, one thread per row, 8 loads in flight
         for (int b = threadIdx.x; b < p.Bp; b += THREADS) {
@@ -648,7 +669,7 @@ __global__ void __launch_bounds__(THREADS) mlp_step_kernel(P p) {
 }
 
 struct Layout {
-  size_t h[MAXL], d[MAXL + 1], g[MAXL], colp[MAXL + 1], am[MAXL], dm[MAXL], rowp, totp, total;
+  size_t h[MAXL], d[MAXL + 1], g[MAXL], colp[MAXL + 1], am[MAXL], dm[MAXL], rowp, totp, rhop, total;
 };
 Layout layout(const OcfMlpStepArgs& a, int* dim) {
   Layout w{};
@@ -670,6 +691,7 @@ Layout layout(const OcfMlpStepArgs& a, int* dim) {
   }
   w.rowp = take((size_t)(a.Np / TT) * a.Bp);
   w.totp = take((size_t)(a.Bp / TT) * (a.Np / TT) * WAVES * 3);
+  w.rhop = take((size_t)(a.Bp / TT) * (a.Np / TT) * WAVES);
   w.total = off;
   return w;
 }
@@ -707,17 +729,22 @@ void check(const OcfMlpStepArgs& a) {
       OCF_CHECK(a.sW1[i] && a.sb1[i] && (a.opt.kind != OCF_OPT_ADAM || (a.sW2[i] && a.sb2[i])),
                 "ocf_mlp_step: optimizer slots");
   OCF_CHECK(a.stats && a.work && a.barrier, "ocf_mlp_step: stats / work / barrier");
+  check_loss(a.loss, a.loss_param, "ocf_mlp_step");
 }
 
-template <typename CT>
-void launch(const OcfMlpStepArgs& a, const P& p, int wgs, hipStream_t s) {
+template <typename CT, int LOSS>
+void launch_loss(const OcfMlpStepArgs& a, const P& p, int wgs, hipStream_t s) {
   switch (a.opt.kind) {
-    case OCF_OPT_ADAGRAD: hipLaunchKernelGGL((mlp_step_kernel<CT, OCF_OPT_ADAGRAD>), dim3(wgs), dim3(THREADS), 0, s, p); break;
-    case OCF_OPT_RMSPROP: hipLaunchKernelGGL((mlp_step_kernel<CT, OCF_OPT_RMSPROP>), dim3(wgs), dim3(THREADS), 0, s, p); break;
-    case OCF_OPT_ADAM: hipLaunchKernelGGL((mlp_step_kernel<CT, OCF_OPT_ADAM>), dim3(wgs), dim3(THREADS), 0, s, p); break;
-    default: hipLaunchKernelGGL((mlp_step_kernel<CT, 0>), dim3(wgs), dim3(THREADS), 0, s, p);
+    case OCF_OPT_ADAGRAD: hipLaunchKernelGGL((mlp_step_kernel<CT, OCF_OPT_ADAGRAD, LOSS>), dim3(wgs), dim3(THREADS), 0, s, p); break;
+    case OCF_OPT_RMSPROP: hipLaunchKernelGGL((mlp_step_kernel<CT, OCF_OPT_RMSPROP, LOSS>), dim3(wgs), dim3(THREADS), 0, s, p); break;
+    case OCF_OPT_ADAM: hipLaunchKernelGGL((mlp_step_kernel<CT, OCF_OPT_ADAM, LOSS>), dim3(wgs), dim3(THREADS), 0, s, p); break;
+    default: hipLaunchKernelGGL((mlp_step_kernel<CT, 0, LOSS>), dim3(wgs), dim3(THREADS), 0, s, p);
   }
   OCF_HIP(hipGetLastError());
+}
+template <typename CT>
+void launch(const OcfMlpStepArgs& a, const P& p, int wgs, hipStream_t s) {
+  OCF_LOSS_SWITCH(a.loss, (launch_loss<CT, LK>(a, p, wgs, s)));
 }
 
 }  // namespace mlp
@@ -764,6 +791,8 @@ extern "C" int ocf_mlp_step(const OcfMlpStepArgs* a, void* stream) {
   p.keep = a->keep; p.seed = a->seed; p.stream = a->stream;
   p.rowp = reinterpret_cast<float*>(ws + w.rowp);
   p.totp = reinterpret_cast<float*>(ws + w.totp);
+  p.rhop = reinterpret_cast<float*>(ws + w.rhop);
+  p.loss_param = a->loss_param;
   for (int j = 0; j < 3; ++j) p.x[j] = a->x[j];
   p.ld_x = a->ld_x; p.rows = a->rows; p.om = a->out_mask; p.tg = a->targets; p.ld_t = a->ld_t;
   for (int i = 0; i <= p.L; ++i) {

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "ocf_internal.h"
+#include "ocf_loss.h"
 
 namespace ocf {
 
@@ -305,6 +306,68 @@ __global__ void __launch_bounds__(256) mse_total_kernel(float* stats, int B, int
   }
 }
 
+// mse_rows_kernel for a loss rho other than MSE: grad = rho'(e) M, and a fourth per-row sum, of rho(e)
+template <int LOSS>
+__global__ void __launch_bounds__(256) loss_rows_kernel(const float* pred, const float* T, const float* M, int64_t ld,
+                                                        int N, float* grad, int64_t ld_g, float* row_stats, int B,
+                                                        float lp) {
+  __shared__ float red[4][256];
+  const int b = blockIdx.x;
+  float sse = 0.f, sae = 0.f, cnt = 0.f, rho = 0.f;
+  for (int n = threadIdx.x; n < N; n += 256) {
+    const int64_t o = (int64_t)b * ld + n;
+    const float y = pred[o], t = T[o];
+    const float e = y - t;
+    sse += e * e;
+    sae += fabsf(e);
+    cnt += (t + y != 0.f) ? 1.f : 0.f;
+    rho += loss_value<LOSS>(e, lp);
+    if (grad) {
+      const float g = loss_grad<LOSS>(e, lp);
+      grad[(int64_t)b * ld_g + n] = M ? g * M[o] : g;
+    }
+  }
+  red[0][threadIdx.x] = sse;
+  red[1][threadIdx.x] = sae;
+  red[2][threadIdx.x] = cnt;
+  red[3][threadIdx.x] = rho;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (threadIdx.x < w)
+      for (int k = 0; k < 4; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x < 4) row_stats[(int64_t)threadIdx.x * B + b] = red[threadIdx.x][0];
+}
+
+// mse_total_kernel with the loss from the rows' sums of rho (row array 3)
+__global__ void __launch_bounds__(256) loss_total_kernel(float* stats, int B, int N) {
+  __shared__ double red[4][256];
+  const float* rows = stats + 4;
+  double v[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int b = threadIdx.x; b < B; b += 256)
+    for (int k = 0; k < 4; ++k) v[k] += (double)rows[(int64_t)k * B + b];
+  for (int k = 0; k < 4; ++k) red[k][threadIdx.x] = v[k];
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (threadIdx.x < w)
+      for (int k = 0; k < 4; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    stats[0] = (float)red[0][0];
+    stats[1] = (float)red[1][0];
+    stats[2] = (float)red[2][0];
+    stats[3] = (float)(red[3][0] / ((double)B * (double)N));
+  }
+}
+
+// the MSE call's fourth row array: the rows' sums of rho are their SSE
+__global__ void __launch_bounds__(256) copy_rows_kernel(const float* src, float* dst, int B) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b < B) dst[b] = src[b];
+}
+
 // the output delta in the compute dtype, zero-padded to [Bp][Np]
 __global__ void __launch_bounds__(256) delta_pack_kernel(const float* g, int64_t ld, int B, int N, void* d, int dt,
                                                          int64_t Np, int64_t Bp) {
@@ -329,6 +392,29 @@ extern "C" int ocf_masked_mse(const float* pred, const float* T, const float* ou
   hipLaunchKernelGGL(mse_rows_kernel, dim3(B), dim3(256), 0, s, pred, T, out_mask, ld, N, out_grad, ld_grad,
                      out_stats + 4, B);
   hipLaunchKernelGGL(mse_total_kernel, dim3(1), dim3(256), 0, s, out_stats, B, N);
+  OCF_HIP(hipGetLastError());
+  OCF_TRY_END
+}
+
+// ocf_masked_mse for any OCF_LOSS_* (ocf.h): MSE runs ocf_masked_mse's two kernels (the same bits)
+extern "C" int ocf_masked_loss(int loss, float loss_param, const float* pred, const float* T, const float* out_mask,
+                               int64_t ld, int B, int N, float* out_grad, int64_t ld_grad, float* out_stats,
+                               void* stream) {
+  OCF_TRY_BEGIN
+  check_loss(loss, loss_param, "ocf_masked_loss");
+  OCF_CHECK(pred && T && out_stats, "ocf_masked_loss: null pointer");
+  OCF_CHECK(B >= 1 && N >= 1 && ld >= N && (!out_grad || ld_grad >= N), "ocf_masked_loss: sizes");
+  hipStream_t s = (hipStream_t)stream;
+  float* rows = out_stats + 4;
+  if (loss == OCF_LOSS_MSE) {
+    hipLaunchKernelGGL(mse_rows_kernel, dim3(B), dim3(256), 0, s, pred, T, out_mask, ld, N, out_grad, ld_grad, rows, B);
+    hipLaunchKernelGGL(mse_total_kernel, dim3(1), dim3(256), 0, s, out_stats, B, N);
+    hipLaunchKernelGGL(copy_rows_kernel, dim3((B + 255) / 256), dim3(256), 0, s, rows, rows + (int64_t)3 * B, B);
+  } else {
+    OCF_LOSS_SWITCH(loss, hipLaunchKernelGGL((loss_rows_kernel<LK>), dim3(B), dim3(256), 0, s, pred, T, out_mask, ld, N,
+                                             out_grad, ld_grad, rows, B, loss_param));
+    hipLaunchKernelGGL(loss_total_kernel, dim3(1), dim3(256), 0, s, out_stats, B, N);
+  }
   OCF_HIP(hipGetLastError());
   OCF_TRY_END
 }

@@ -22,6 +22,7 @@
 
 #include "ocf_epilogues.h"
 #include "ocf_internal.h"
+#include "ocf_loss.h"
 
 namespace ocf {
 
@@ -152,6 +153,8 @@ __device__ __forceinline__ void reduce_groups(const float (&acc)[V], float* red,
 // (written by an earlier launch).
 // solo: the row's only chunk is this workgroup's -- no stores to hand off, no counter: its own column sums
 // (own) and stats total (own_st, threads 0..2) are the row's, added to 0 as the chunk loop would.
+// NS: the stats values a chunk carries (LossStats: 3, or 4 with the sum of rho of a loss other than MSE)
+template <int NS>
 __device__ __forceinline__ void dec_row_tail(const OcfGatherArgs& a, const OcfRowsReduceArgs& r, int b,
                                              const float* a_sh, const uint8_t* mk_sh, bool stash, bool solo,
                                              const float* own, float own_st, uint32_t* enc_arrive) {
@@ -179,7 +182,7 @@ __device__ __forceinline__ void dec_row_tail(const OcfGatherArgs& a, const OcfRo
   float sq[4];                                  // the first 4 chunks' stats, loaded with the partials
 #pragma unroll
   for (int k = 0; k < 4; ++k)
-    sq[k] = threadIdx.x < 3 && c0 + k < c1 ? ld_sc1(r.chunk_stats, (int64_t)(c0 + k) * 4 + threadIdx.x) : 0.f;
+    sq[k] = threadIdx.x < NS && c0 + k < c1 ? ld_sc1(r.chunk_stats, (int64_t)(c0 + k) * 4 + threadIdx.x) : 0.f;
   for (int x = threadIdx.x, i = 0; x < r.H; x += RG_THREADS, ++i) {
     float v = 0.f;
     if (solo) v += own[i];
@@ -203,7 +206,7 @@ __device__ __forceinline__ void dec_row_tail(const OcfGatherArgs& a, const OcfRo
   }
   if (threadIdx.x < 4) {
     float v = 0.f;
-    if (threadIdx.x < 3) {
+    if (threadIdx.x < NS) {
       if (solo) v += own_st;
 #pragma unroll
       for (int k = 0; k < 4; ++k)
@@ -326,13 +329,14 @@ __device__ __forceinline__ void dec_row_abandon(const OcfGatherArgs& a, const Oc
 // stores nothing) and reads their write-through partials with L1-bypassing loads.  Deadlock-free: the encoder
 // chunks are the launch's first workgroups and workgroups dispatch in index order, so a waiting decoder chunk's
 // producers are resident or done.
-template <typename WT, typename HT, int G, int PPL>
+template <typename WT, typename HT, int G, int PPL, int LOSS>
 __device__ __forceinline__ void decoder_chunk(const OcfGatherArgs& a, const OcfRowsReduceArgs& jr, const int c,
                                               const bool first_wg, float* red, const EncDecSync& sy) {
   constexpr int E = EPc<WT>::v;
   constexpr int V = PPL * E;
   constexpr int NG = RG_THREADS / G;
-  __shared__ float st[NG][3];
+  constexpr int NS = LossStats<LOSS>::N;
+  __shared__ float st[NG][NS];
   const int b = a.ch_row[c], j0 = a.ch_j0[c], j1 = a.ch_j1[c];
   const int grp = threadIdx.x / G, l = threadIdx.x % G;
   const int r = a.rows[b];
@@ -430,6 +434,7 @@ __device__ __forceinline__ void decoder_chunk(const OcfGatherArgs& a, const OcfR
 #pragma unroll
   for (int k = 0; k < V; ++k) acc[k] = 0.f;
   float sse = 0.f, sae = 0.f, cnt = 0.f;
+  [[maybe_unused]] float rho = 0.f;            // (a loss other than MSE) the sum of rho(err)
   for (int j = j0 + grp; j < j1; j += NG * RG_UD) {
     uint4 w[RG_UD][PPL];
     bool lv[RG_UD];
@@ -471,11 +476,13 @@ __device__ __forceinline__ void decoder_chunk(const OcfGatherArgs& a, const OcfR
       if (lv[u]) {
         const float yh = m * (dot[u] + bn[u]);
         const float err = yh - tc[u];
-        d = err * m;
+        if constexpr (LOSS == OCF_LOSS_MSE) d = err * m;
+        else d = loss_grad<LOSS>(err, a.loss_param) * m;
         if (l == 0) {
           sse += err * err;
           sae += fabsf(err);
           cnt += (tc[u] + yh != 0.f) ? 1.f : 0.f;
+          if constexpr (LOSS != OCF_LOSS_MSE) rho += loss_value<LOSS>(err, a.loss_param);
           if (a.d_out) store_ct(a.d_out, a.d_dtype, (int64_t)b * a.ld_d + nc[u], d);
         }
       }
@@ -493,13 +500,14 @@ __device__ __forceinline__ void decoder_chunk(const OcfGatherArgs& a, const OcfR
     st[grp][0] = sse;
     st[grp][1] = sae;
     st[grp][2] = cnt;
+    if constexpr (LOSS != OCF_LOSS_MSE) st[grp][3] = rho;
   }
   // (fold) a row of one chunk keeps its sums in registers: nothing to hand off
   const bool solo = fold && jr.row_cptr[b + 1] - jr.row_cptr[b] == 1;
   float own[RG_XPT];
   reduce_groups<G, V, E, PPL>(acc, red, a.part, c, a.H, grp, l, fold, solo, own);
   float own_st = 0.f;
-  if (threadIdx.x < 3) {
+  if (threadIdx.x < NS) {
     float v = 0.f;
     for (int g = 0; g < NG; ++g) v += st[g][threadIdx.x];
     own_st = v;
@@ -510,17 +518,17 @@ __device__ __forceinline__ void decoder_chunk(const OcfGatherArgs& a, const OcfR
       a.chunk_stats[(int64_t)c * 4 + threadIdx.x] = v;
     }
   }
-  if (fold) dec_row_tail(a, jr, b, a_sh, mk_sh, a.enc_part != nullptr, solo, own, own_st, enc_arrive);
+  if (fold) dec_row_tail<NS>(a, jr, b, a_sh, mk_sh, a.enc_part != nullptr, solo, own, own_st, enc_arrive);
 }
 
 // (f16: 133 VGPRs, bf16: 163 -- 3 waves per SIMD.  Capped at 128 by amdgpu_waves_per_eu(4) the f16 form spills 20 B
 // per lane and the ML-20M step goes 0.381 -> 0.524 ms, same box, profiles/r05_decoder_cap128_ab.jsonl; an LDS-resident
 // hidden row instead of the per-lane pieces does not lower the peak.  Round 4: 162 VGPRs, 144 B spilled, 0.388 ->
 // 0.523 ms)
-template <typename WT, typename HT, int G, int PPL>
+template <typename WT, typename HT, int G, int PPL, int LOSS>
 __global__ void __launch_bounds__(RG_THREADS) gather_decoder_kernel(OcfGatherArgs a, OcfRowsReduceArgs jr) {
   __shared__ float red[(RG_THREADS / G) * RG_MAX_H];
-  decoder_chunk<WT, HT, G, PPL>(a, jr, blockIdx.x, blockIdx.x == 0, red, EncDecSync{});
+  decoder_chunk<WT, HT, G, PPL, LOSS>(a, jr, blockIdx.x, blockIdx.x == 0, red, EncDecSync{});
 }
 
 // The encoder and the decoder as ONE launch (ocf_gather_encdec): workgroups [0, e.n_chunks) are the encoder's
@@ -528,13 +536,13 @@ __global__ void __launch_bounds__(RG_THREADS) gather_decoder_kernel(OcfGatherArg
 // (per-row arrival counters enc_arrive, reset by the row's last decoder chunk) instead of after the whole encoder
 // launch.  Needs the decoder's folded row reduction (its last chunk per row resets the counter) and the same
 // chunk table for both (train batches: inputs = targets).
-template <typename WT, typename HT, int G, int PPL>
+template <typename WT, typename HT, int G, int PPL, int LOSS>
 __global__ void __launch_bounds__(RG_THREADS) gather_encdec_kernel(OcfGatherArgs e, OcfGatherArgs d,
                                                                    OcfRowsReduceArgs jr, EncDecSync sy) {
   __shared__ float red[(RG_THREADS / G) * RG_MAX_H];
   const int bx = blockIdx.x;
   if (bx < e.n_chunks) encoder_chunk<WT, G, PPL, RG_UE>(e, bx, red, sy.enc_arrive);
-  else decoder_chunk<WT, HT, G, PPL>(d, jr, bx - e.n_chunks, bx == e.n_chunks, red, sy);
+  else decoder_chunk<WT, HT, G, PPL, LOSS>(d, jr, bx - e.n_chunks, bx == e.n_chunks, red, sy);
 }
 
 // The row-resident form of the encoder -> decoder launch (ocf_gather_encdec, 16-bit weights; tuning
@@ -610,7 +618,7 @@ __device__ __forceinline__ float rr_sum_slabs(const float* s, int splits, int64_
 // e: the encoder's gather arguments (RR_FULL, RR_ENC_RAW); d: the decoder's (RR_FULL, RR_DEC_RAW; its rows /
 // lboff / rp give the batch rows in every mode); r: the row reduction (GRAD_ACT for RR_FULL, RAW for the others);
 // hb: the hidden epilogue over the all-reduced slabs (RR_DEC_RAW)
-template <typename WT, typename HT, int G, int PPL, int T, int MODE>
+template <typename WT, typename HT, int G, int PPL, int T, int MODE, int LOSS>
 __global__ void __launch_bounds__(T) gather_rowres_kernel(OcfGatherArgs e, OcfGatherArgs d, OcfRowsReduceArgs r,
                                                           OcfBiasActArgs hb) {
   constexpr int E = EPc<WT>::v;
@@ -622,7 +630,8 @@ __global__ void __launch_bounds__(T) gather_rowres_kernel(OcfGatherArgs e, OcfGa
   __shared__ float h_sh[RG_MAX_H];
   __shared__ float a_sh[RG_MAX_H];
   __shared__ uint8_t mk_sh[RG_MAX_H];
-  __shared__ float st_sh[NG][3];
+  constexpr int NS = LossStats<LOSS>::N;
+  __shared__ float st_sh[NG][NS];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int grp = tid / G, l = tid % G;
   const OcfGatherArgs& q = MODE == RR_ENC_RAW ? e : d;     // (the batch rows)
@@ -787,6 +796,7 @@ __global__ void __launch_bounds__(T) gather_rowres_kernel(OcfGatherArgs e, OcfGa
 #pragma unroll
     for (int k = 0; k < V; ++k) acc[k] = 0.f;
     float sse = 0.f, sae = 0.f, cnt = 0.f;
+    [[maybe_unused]] float rho = 0.f;          // (a loss other than MSE) the sum of rho(err)
     for (int j = grp; j < n_e; j += NG * RR_UD) {
       // this iteration's entries (their W_out rows were requested at the end of the previous one)
       bool lv[RR_UD];
@@ -828,11 +838,13 @@ __global__ void __launch_bounds__(T) gather_rowres_kernel(OcfGatherArgs e, OcfGa
         if (lv[u]) {
           const float yh = m * (dot[u] + bn[u]);
           const float err = yh - tc[u];
-          dl = err * m;
+          if constexpr (LOSS == OCF_LOSS_MSE) dl = err * m;
+          else dl = loss_grad<LOSS>(err, d.loss_param) * m;
           if (l == 0) {
             sse += err * err;
             sae += fabsf(err);
             cnt += (tc[u] + yh != 0.f) ? 1.f : 0.f;
+            if constexpr (LOSS != OCF_LOSS_MSE) rho += loss_value<LOSS>(err, d.loss_param);
             if (d.d_out) store_ct(d.d_out, d.d_dtype, (int64_t)b * d.ld_d + nc[u], dl);
           }
         }
@@ -851,6 +863,7 @@ __global__ void __launch_bounds__(T) gather_rowres_kernel(OcfGatherArgs e, OcfGa
       st_sh[grp][0] = sse;
       st_sh[grp][1] = sae;
       st_sh[grp][2] = cnt;
+      if constexpr (LOSS != OCF_LOSS_MSE) st_sh[grp][3] = rho;
     }
     __syncthreads();                 // (every wave is done reading red's encoder sums: the epilogue's barrier)
     rr_wave_sums<G, V, E, PPL>(acc, red, l, lane, w);
@@ -874,7 +887,7 @@ __global__ void __launch_bounds__(T) gather_rowres_kernel(OcfGatherArgs e, OcfGa
   }
   if (tid < 4) {
     float v = 0.f;
-    if (tid < 3)
+    if (tid < NS)
       for (int g = 0; g < NG; ++g) v += st_sh[g][tid];
     r.stats_part[(int64_t)b * 4 + tid] = v;
     if (tid == 0 && r.row_sse) r.row_sse[b] = v;
@@ -917,7 +930,7 @@ __global__ void __launch_bounds__(256) rows_reduce_kernel(OcfRowsReduceArgs a) {
   }
   if (a.chunk_stats && threadIdx.x < 4) {
     float v = 0.f;
-    if (threadIdx.x < 3)
+    if (threadIdx.x < (a.stats4 ? 4 : 3))      // (stats4: the chunks' sums of rho, a loss other than MSE)
       for (int c = c0; c < c1; c += 8) {
         float q[8];
 #pragma unroll
@@ -980,7 +993,8 @@ template <typename WT, typename HT> struct Dec {
     static void go(const OcfGatherArgs& a, hipStream_t s) {
       OcfRowsReduceArgs r{};
       if (a.jr && a.row_arrive) r = *a.jr;
-      hipLaunchKernelGGL((gather_decoder_kernel<WT, HT, G, P>), dim3(a.n_chunks), dim3(RG_THREADS), 0, s, a, r);
+      OCF_LOSS_SWITCH(a.loss, hipLaunchKernelGGL((gather_decoder_kernel<WT, HT, G, P, LK>), dim3(a.n_chunks),
+                                                 dim3(RG_THREADS), 0, s, a, r));
     }
   };
 };
@@ -989,7 +1003,8 @@ template <typename WT, typename HT>
 void launch_encdec(int G, int ppl, const OcfGatherArgs& e, const OcfGatherArgs& d, const EncDecSync& sy, hipStream_t s) {
   OcfRowsReduceArgs r = *d.jr;
   const dim3 grid(e.n_chunks + d.n_chunks), blk(RG_THREADS);
-#define OCF_ED(GG, PP) hipLaunchKernelGGL((gather_encdec_kernel<WT, HT, GG, PP>), grid, blk, 0, s, e, d, r, sy)
+#define OCF_ED(GG, PP) \
+  OCF_LOSS_SWITCH(d.loss, hipLaunchKernelGGL((gather_encdec_kernel<WT, HT, GG, PP, LK>), grid, blk, 0, s, e, d, r, sy))
   if (G == 64 && ppl == 1) OCF_ED(64, 1);
   else if (G == 64 && ppl == 2) OCF_ED(64, 2);
   else if (G == 32 && ppl == 1) OCF_ED(32, 1);
@@ -1003,11 +1018,12 @@ void launch_encdec(int G, int ppl, const OcfGatherArgs& e, const OcfGatherArgs& 
 #undef OCF_ED
 }
 
-template <typename WT, typename HT, int T, int MODE>
+template <typename WT, typename HT, int T, int MODE, int LOSS>
 void launch_rowres_t(int G, int ppl, const OcfGatherArgs& e, const OcfGatherArgs& d, const OcfRowsReduceArgs& r,
                      const OcfBiasActArgs& hb, hipStream_t s) {
   const dim3 grid(r.Bp), blk(T);
-#define OCF_RR(GG, PP) hipLaunchKernelGGL((gather_rowres_kernel<WT, HT, GG, PP, T, MODE>), grid, blk, 0, s, e, d, r, hb)
+#define OCF_RR(GG, PP) \
+  hipLaunchKernelGGL((gather_rowres_kernel<WT, HT, GG, PP, T, MODE, LOSS>), grid, blk, 0, s, e, d, r, hb)
   if (G == 32 && ppl == 2) OCF_RR(32, 2);
   else if (G == 64 && ppl == 2) OCF_RR(64, 2);
   else if (G == 64 && ppl == 1) OCF_RR(64, 1);
@@ -1028,10 +1044,15 @@ void launch_rowres(int dtype, int H, int T, const OcfGatherArgs& e, const OcfGat
   } else if (!(dtype == OCF_F16 ? gather_shape<_Float16>(H, G, ppl) : gather_shape<__bf16>(H, G, ppl))) {
     throw std::runtime_error("row gather (row-resident): unsupported H");
   }
+  // (the losses other than MSE: ocf_gather_encdec's launch only; a feature rank's phases are MSE, checked there)
   auto go = [&](auto wt) {
     using WT = decltype(wt);
-    if (T == 256) launch_rowres_t<WT, WT, 256, MODE>(G, ppl, e, d, r, hb, s);
-    else launch_rowres_t<WT, WT, 1024, MODE>(G, ppl, e, d, r, hb, s);
+    if constexpr (MODE == RR_FULL) {
+      OCF_LOSS_SWITCH(d.loss, (launch_rowres_t<WT, WT, 1024, MODE, LK>(G, ppl, e, d, r, hb, s)));
+    } else {
+      if (T == 256) launch_rowres_t<WT, WT, 256, MODE, OCF_LOSS_MSE>(G, ppl, e, d, r, hb, s);
+      else launch_rowres_t<WT, WT, 1024, MODE, OCF_LOSS_MSE>(G, ppl, e, d, r, hb, s);
+    }
   };
   if (dtype == OCF_F32) go(float{});
   else if (dtype == OCF_F16) go(_Float16{});
@@ -1081,6 +1102,7 @@ extern "C" int ocf_gather_decoder(const OcfGatherArgs* args, void* stream) {
   OCF_CHECK(!a.enc_part || (a.enc_cptr && a.bias_h && (a.keep >= 1.f || a.mask_out) && a.a_out),
             "ocf_gather_decoder: enc_part needs enc_cptr, bias_h, a_out and (with dropout) mask_out");
   OCF_CHECK(!a.jr == !a.row_arrive, "ocf_gather_decoder: jr and row_arrive go together");
+  check_loss(a.loss, a.loss_param, "ocf_gather_decoder");
   if (a.jr) {
     const OcfRowsReduceArgs& r = *a.jr;
     OCF_CHECK(r.mode == OCF_REDUCE_GRAD_ACT && r.part == a.part && r.chunk_stats == a.chunk_stats && r.H == a.H &&
@@ -1129,6 +1151,7 @@ extern "C" int ocf_gather_encdec(const OcfGatherArgs* enc, const OcfGatherArgs* 
   OCF_CHECK(d.enc_part == e.part && d.enc_cptr && d.bias_h && (d.keep >= 1.f || d.mask_out) && d.a_out,
             "ocf_gather_encdec: dec.enc_part must be enc.part, with enc_cptr, bias_h, a_out (and mask_out)");
   OCF_CHECK(d.jr && d.row_arrive, "ocf_gather_encdec: the decoder's folded row reduction (jr, row_arrive) is required");
+  check_loss(d.loss, d.loss_param, "ocf_gather_encdec");
   OCF_CHECK(e.ch_row == d.ch_row && e.ch_j0 == d.ch_j0 && e.ch_j1 == d.ch_j1 && e.n_chunks == d.n_chunks &&
                 e.rows == d.rows && e.lboff == d.lboff && e.rp == d.rp,
             "ocf_gather_encdec: the encoder and the decoder must share the batch's chunk table");

@@ -17,6 +17,9 @@ void order(void* ev, hipStream_t from, hipStream_t to) {
 extern "C" int ocf_rank_step(const OcfRankStepArgs* a, int phase, void* stream) {
   OCF_TRY_BEGIN
   OCF_CHECK(a != nullptr && phase >= 0 && phase <= 3, "ocf_rank_step: arguments / phase 0..3");
+  // (the rank phases' stats path -- RAW row sums, ocf_stats_finalize over the shards -- carries no sum of rho)
+  OCF_CHECK(a->dec.loss == OCF_LOSS_MSE, "ocf_rank_step: only OCF_LOSS_MSE (dec.loss = 0) is implemented for "
+                                         "feature-parallel rank steps");
   hipStream_t s = (hipStream_t)stream, side = (hipStream_t)a->side;
   auto ok = [](int rc) { OCF_CHECK(rc == 0, ocf_last_error()); };
   switch (phase) {

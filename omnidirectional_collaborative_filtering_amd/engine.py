@@ -27,7 +27,7 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, losses
 from ._lib import OcfGemmArgs, OcfScatterArgs
 
 # while Engine._recorded_step runs: every library call of the step as (name, args) -- the template of the
@@ -137,6 +137,9 @@ class Engine:
         self.mlp_trace = None
         self.mlp_wgs = 0                        # ocf_mlp_step's grid (0: the library's choice)
         self.step_paths = {"one_call": 0, "general": 0}   # fast_train_step's choices (diagnostics)
+        # the general path's decoder launches (diagnostics): ocf_gather_encdec in its row-resident / chunked form,
+        # ocf_gather_decoder
+        self.gather_launches = {"rowres": 0, "encdec": 0, "decoder": 0}
         self.act = _lib.ACT[activation]
         self.activation = activation
         self.dropout = dropout
@@ -162,6 +165,9 @@ class Engine:
         self.master_sync = None
         self.opt = None
         self.slots = []
+        # the training loss (losses.Loss; Model.compile -> set_loss): every kernel that computes the masked loss
+        # is specialised on its code, the gradient scale is loss.grad_num / (B N)
+        self.loss = losses.MeanSquaredError()
         self._alloc_params()
         self._alloc_workspace()
         self.init_weights(np.random.RandomState(self.seed))
@@ -264,6 +270,25 @@ class Engine:
             self.b[i].zero_()
             self.b[i][: self.real_dims[i + 1]] = bb
         self._refresh_shadows()
+
+    def set_loss(self, loss):
+        """The training loss (losses.Loss).  The multi-GPU layouts reduce their statistics over the ranks without
+        the sum of rho(e), so they take the squared loss only."""
+        if loss.code != _lib.LOSS_MSE and (self.comm is not None or self.dp_world > 1):
+            raise NotImplementedError("loss %r is not implemented for the feature-parallel / data-parallel layouts "
+                                      "(only 'mean_squared_error' is)" % (loss.name,))
+        if loss != self.loss:
+            self._plan = None
+            self._bufgen += 1
+        self.loss = loss
+
+    def _mse(self):
+        return self.loss.code == _lib.LOSS_MSE
+
+    def _gscale(self):
+        """the constant of the loss gradient folded into the weight / bias-gradient epilogues: 2 / (B N) for MSE
+        (delta = e m), 1 / (B N) for the others (delta = rho'(e) m)"""
+        return self.loss.grad_num / ((self.rows_real or self.B) * self.N_total)
 
     def set_optimizer(self, opt):
         self.opt = opt
@@ -792,8 +817,9 @@ class Engine:
         if self.keep < 1.0:
             for i in range(len(self.H)):
                 a.mask[i] = ptr(self.mask[i])
-        o = self.opt.step_params(2.0 / ((self.rows_real or self.B) * self.N_total), 0.0)
+        o = self.opt.step_params(self._gscale(), 0.0)
         a.opt = o
+        a.loss, a.loss_param = self.loss.code, self.loss.param     # (not MSE: stats[3] = the sum of rho)
         a.trace = ptr(self.mlp_trace)          # (diagnostics: tools/mlp_trace.py)
         a.wgs = self.mlp_wgs
         self._grow_stats(self.n_stats + 1)
@@ -1002,6 +1028,7 @@ class Engine:
         g.flag = self.gt.get("flag") or ptr(self.tflag)
         g.h, g.h_dtype, g.bias, g.aux = ptr(self.h[L - 1]), self.cdt, ptr(self.b[L]), self.gt["aux"]
         g.chunk_stats = ptr(cst)
+        g.loss, g.loss_param = self.loss.code, self.loss.param
         ef, self._enc_fused = self._enc_fused, None
         if ef is not None:
             g.enc_part, g.enc_cptr, g.keep, g.stream = ef["enc_part"], ef["enc_cptr"], ef["keep"], ef["stream"]
@@ -1023,6 +1050,7 @@ class Engine:
             r = self._reduce_args(tab, part, HpL, _lib.REDUCE_RAW)
             r.out = ptr(self.dhpre if (with_grad and self.comm is not None) else self.dh_raw)
         r.chunk_stats, r.stats_part, r.row_sse = ptr(cst), ptr(self.stats_rows), ptr(self.row_sse_rows)
+        r.stats4 = 0 if self._mse() else 1      # (the chunks' sums of rho -> stats_rows[b][3])
         self._reduce_job = None
         self._dec_reduced = False
         fold = (with_grad and self.comm is None and self._fused_step and self.fold_reduce and self._folds()
@@ -1035,6 +1063,8 @@ class Engine:
             # profiles/r05_dual_large/); small weights with k >= 2: two launches with the reduction riding in
             # the first (the measured round-4 form)
             in_dec = self.k == 1 or self.Np // TILE * 48 >= 8192
+        if not self._mse():
+            in_dec = True                 # (the reduction as a dW job sums three stats per chunk: no sum of rho)
         if fold and in_dec and tab["n_chunks"] > 0:
             g.jr, g.row_arrive = ctypes.addressof(r), ptr(self.row_arrive)
             self._last_jr = r             # (kept alive: the recorded step's decoder arguments point at it)
@@ -1049,6 +1079,7 @@ class Engine:
                     and et["lboff"] == tab["lboff"]):
                 # (one launch: the caller's dec_gemm_mse phase times both, enc_gemm records nothing)
                 call("ocf_gather_encdec", ea, g, ptr(self.enc_arrive), cur_stream())
+                self.gather_launches["rowres" if self._rowres() else "encdec"] += 1
                 return self._after_decoder(g, fold, r)
             dec_phase = self.__dict__.get("_active_phase")
             with self.phase("enc_gemm"):
@@ -1056,12 +1087,13 @@ class Engine:
             if dec_phase is not None:
                 dec_phase.restart()
         call("ocf_gather_decoder", g, cur_stream())
+        self.gather_launches["decoder"] += 1
         return self._after_decoder(g, fold, r)
 
     def _after_decoder(self, g, fold, r):
         if g.jr:
             pass                          # done by the decoder's last chunk of each row
-        elif fold:
+        elif fold and self._mse():
             self._reduce_job = r          # rides in the dW_out launch (OcfGemmArgs jr), see _backward_gather
             self._last_jr = r             # (kept alive: the recorded step's dW_out arguments point at it)
         else:
@@ -1071,7 +1103,7 @@ class Engine:
         """Decoder (dense GEMM with the fused masked-MSE epilogue, or the row gather for sparse
         batches); stats -> stats_hist[n_stats]."""
         L = len(self.H)
-        gscale = 2.0 / ((self.rows_real or self.B) * self.N_total)
+        gscale = self._gscale()
         with self.phase("dec_gemm_mse"):
             if self.gt is not None:
                 self._output_gather(with_grad, gscale)
@@ -1081,7 +1113,12 @@ class Engine:
                 sp, n_sp, rs, n_rs = self.stats_part, self.n_tiles * (self.Bp // TILE), self.row_sse_part, self.n_tiles
         self._grow_stats(self.n_stats + 1)
         dst = self.stats_hist[self.n_stats]
-        if with_grad and self._folds():
+        if not self._mse():
+            # the sum of rho(e) from the partials' fourth float into the row's slot 3, after the finalisation
+            # (which zeroes it), both on this stream
+            call("ocf_stats_finalize", ptr(sp), n_sp, ptr(rs), n_rs, self.Bp, ptr(dst), cur_stream())
+            call("ocf_loss_sum", ptr(sp), n_sp, ptr(dst) + 12, cur_stream())
+        elif with_grad and self._folds():
             # finalized by the output-layer weight-gradient launch (OcfGemmArgs js_*)
             self._stats_pending = (sp, n_sp, rs, n_rs, self.Bp, dst)
         elif self.side is not None:
@@ -1113,7 +1150,8 @@ class Engine:
                    h_out=self.d_out if with_grad else None, h_dtype=self.cdt, ld_out=self.Np,
                    db_part=self.db_out_part if with_grad else None, ld_db=self.Np,
                    opt=_lib.OcfOptParams(0, 0, 0, 0, 0, 0, gscale),
-                   stats_part=self.stats_part, row_sse_part=self.row_sse_part)
+                   stats_part=self.stats_part, row_sse_part=self.row_sse_part,
+                   loss=self.loss.code, loss_param=self.loss.param)
 
     def predict_dense(self, out_mask, out):
         """PREDICT epilogue: out[B][N] = out_mask * (h W + b)."""
@@ -1357,7 +1395,7 @@ class Engine:
         the caller all-reduces and calls apply_grads()."""
         s = cur_stream()
         L, Bp = len(self.H), self.Bp
-        gscale = 2.0 / ((self.rows_real or self.B) * self.N_total)
+        gscale = self._gscale()
         fused = grads_out is None
         op = self.opt.step_params(1.0, self.l2) if fused else None
         self._bias_op = self.opt.step_params(1.0, 0.0) if fused else None   # l2 regularises kernels only
@@ -1707,7 +1745,8 @@ class Engine:
         if not (self.comm is None and self.dp_world == 1 and len(self.H) == 1 and self.sparse_ok and self.use_sparse
                 and self.sparse_dw and self.epoch_row_lists and self.epoch_scatter and
                 self.fold_reduce and self.fuse_enc_epilogue and not self.l2 and all(self.trainable) and
-                self.grad_hook is None and self.master_sync is None):
+                self.grad_hook is None and self.master_sync is None and self._mse()):
+            # (a loss other than MSE: the general path, whose output_loss collects the sum of rho)
             return None
         return key
 
@@ -1787,7 +1826,7 @@ class Engine:
         if self.opt.kind != _lib.OPT_ADAM and not self.opt.decay and self._plan is not None \
                 and self._plan.get("ready"):
             return stream, row, None, None     # constant optimizer scalars: the template's stand
-        gscale = 2.0 / ((self.rows_real or self.B) * self.N_total)
+        gscale = self._gscale()
         op = self.opt.step_params(1.0, self.l2)
         o = _lib.OcfOptParams(op.kind, op.lr, op.eps, op.rho, op.beta2, op.l2, gscale)
         return stream, row, o, self.opt.step_params(1.0, 0.0)
@@ -2111,8 +2150,10 @@ class Engine:
         self.output_loss(with_grad=False)
         self._join()
 
-    def take_stats(self):
-        """host copy of the per-step stats recorded since the last call: [steps, 4 + Bp]."""
+    def take_stats(self, loss_sums=False):
+        """host copy of the per-step stats recorded since the last call: [steps, 4 + Bp].  loss_sums: also
+        return the steps' sums of rho(e) [steps] (the device rows' slot 3 under a loss other than MSE; under MSE
+        the SSE column)."""
         self._flush_stats()
         st = self.stats_hist[: self.n_stats]
         pen = self.pen_hist[: self.n_stats]
@@ -2127,7 +2168,8 @@ class Engine:
         # the steps just read back surfaces here, at every epoch end, not only at the next library call
         _lib.call("ocf_check_async")
         # column 3 (0 from the loss epilogues) carries the step's l2 penalty
+        rho = out[:, 0].copy() if self._mse() else out[:, 3].copy()
         out[:, 3] = pen.double().sum(1).cpu().numpy()
         self.pen_hist[: self.n_stats].zero_()
         self.n_stats = 0
-        return out
+        return (out, rho) if loss_sums else out

@@ -4,7 +4,8 @@ train_on_batch, test_on_batch, save, metrics_names, get_weights / set_weights.
 
 Graph (model.py:43-99):  x = concat([data, observed_mask?, second_mask?]);
 L x [Dense(H, act) -> Dropout(p, noise_shape=[B, H])] ; y = output_mask * Dense(N, linear)(x)
-Loss: Keras 'mean_squared_error' (train.py:49).  Everything runs through engine.Engine on the GPU.
+Loss: Keras 'mean_squared_error' (train.py:49), or 'mean_absolute_error' / 'huber' / 'logcosh' (losses.py).
+Everything runs through engine.Engine on the GPU.
 """
 from __future__ import annotations
 
@@ -13,6 +14,7 @@ import time
 import numpy as np
 import torch
 
+from . import losses
 from . import metrics as M
 from . import optimizers
 from .data_reader import BatchGenerator
@@ -52,6 +54,7 @@ class Model(object):
         self.use_causal_info = use_causal_info
         self.use_both_masks = use_both_masks
         self.optimizer = None
+        self.loss = engine.loss
         self.metric_names = []
         self.rating_range = float(rating_range)
         self.stop_training = False
@@ -63,6 +66,9 @@ class Model(object):
         """Row data parallelism (parallel.DataParallel): call on every rank after torch.distributed is
         initialised and the model is compiled; rank 0's weights are broadcast."""
         from .parallel import DataParallel
+        if int(world) > 1 and self.loss.code != losses.MeanSquaredError.code:
+            raise NotImplementedError("loss %r is not implemented under data parallelism (only "
+                                      "'mean_squared_error' is)" % (self.loss.name,))
         if self.engine.comm is not None:
             raise ValueError("data parallelism over a feature-parallel (column-sharded) engine is not supported")
         self.rank, self.world = int(rank), int(world)
@@ -99,9 +105,17 @@ class Model(object):
             self.engine.train_step()
 
     # ------------------------------------------------------------------ compile
-    def compile(self, optimizer, loss="mean_squared_error", metrics=None, rating_range=None):
-        if loss not in ("mean_squared_error", "mse"):
-            raise NotImplementedError("only the masked 'mean_squared_error' loss of train.py:49 is implemented")
+    def compile(self, optimizer, loss="mean_squared_error", metrics=None, rating_range=None, loss_params=None):
+        """loss: 'mean_squared_error' / 'mse' (train.py:49), 'mean_absolute_error' / 'mae', 'huber' (with
+        loss_params={"delta": d}, default 1.0), 'logcosh', or a losses.Loss instance.  ValueError for an unknown
+        name or a bad delta; NotImplementedError for a Keras loss that is not built, and for any loss but the
+        squared one on a multi-GPU layout (feature or data parallel)."""
+        loss = losses.get(loss, loss_params)
+        if loss.code != losses.MeanSquaredError.code and self.dp is not None:
+            raise NotImplementedError("loss %r is not implemented under data parallelism (only "
+                                      "'mean_squared_error' is)" % (loss.name,))
+        self.engine.set_loss(loss)
+        self.loss = loss
         self.optimizer = optimizers.get(optimizer)
         self.engine.set_optimizer(self.optimizer)
         self.metric_names = [M.metric_name(m) for m in (metrics or [])]
@@ -112,19 +126,26 @@ class Model(object):
     def metrics_names(self):
         return ["loss"] + list(self.metric_names)
 
+    def _take_stats(self):
+        """Engine.take_stats with the steps' sums of rho(e), the compiled loss's numerator"""
+        return self.engine.take_stats(loss_sums=True)
+
     def _logs_from_stats(self, st, rows=None):
-        """st: [steps, 4 + Bp] device stats -> epoch-mean logs.  rows: the row count of every step's batch
-        (None: all full) -- Keras weights each batch's values by its size (BaseLogger for the training
-        logs, _test_loop for evaluation), which matters only for Model.fit's trailing partial batch."""
+        """st: ([steps, 4 + Bp] device stats, [steps] sums of rho(e)) from _take_stats -> epoch-mean logs.  rows:
+        the row count of every step's batch (None: all full) -- Keras weights each batch's values by its size
+        (BaseLogger for the training logs, _test_loop for evaluation), which matters only for Model.fit's trailing
+        partial batch."""
         e = self.engine
         B = e.B
+        st, rho = st
         rows = [B] * len(st) if rows is None else list(rows)
         assert len(rows) == len(st)
         out = {k: [] for k in self.metrics_names}
-        for row, b in zip(st, rows):
+        for row, lsum, b in zip(st, rho, rows):
             sse, sae, cnt = row[0], row[1], row[2]
-            # Keras' total loss = MSE + the kernels' l2 penalty (row[3], 0 without l2); metrics have none
-            out["loss"].append(sse / (b * e.N_total) + row[3])
+            # Keras' total loss = the mean of rho(e) over all b * N elements (MSE: rho = e^2, the SSE) + the
+            # kernels' l2 penalty (row[3], 0 without l2); metrics have none
+            out["loss"].append(lsum / (b * e.N_total) + row[3])
             for name in self.metric_names:
                 out[name].append(M.from_stats(name, sse, sae, cnt, row[4:], B, e.N_total, self.rating_range, rows=b))
         w = np.asarray(rows, np.float64)
@@ -183,12 +204,12 @@ class Model(object):
     def train_on_batch(self, x, y):
         self._load((x, y))
         self.engine.train_step()
-        return self._finish(self.engine.take_stats())
+        return self._finish(self._take_stats())
 
     def test_on_batch(self, x, y):
         self._load((x, y))
         self.engine.eval_step()
-        return self._finish(self.engine.take_stats())
+        return self._finish(self._take_stats())
 
     def _finish(self, st):
         logs = self._logs_from_stats(st)
@@ -204,7 +225,7 @@ class Model(object):
             t0 = time.time()
             for _ in range(steps // self.world if self.world > 1 else steps):
                 self._train_one(generator)
-            logs = self._logs_from_stats(self.engine.take_stats())
+            logs = self._logs_from_stats(self._take_stats())
             if self.world > 1:
                 logs = self._mean_over_ranks(logs)
             if validation_data is not None:
@@ -238,7 +259,7 @@ class Model(object):
         for _ in range(steps):
             self._pull(generator)
             self.engine.eval_step()
-        return self._finish(self.engine.take_stats())
+        return self._finish(self._take_stats())
 
     def evaluate_sse(self, generator, steps):
         """Fused form of train.py:225-255: (sum of squared errors, sum of target_count)."""
@@ -445,13 +466,13 @@ class Model(object):
             for s0, b in tb:
                 self._load_rows(xd, yd, rows_of(idx_d[s0:s0 + b], b), b)
                 e.train_step()
-            logs = self._logs_from_stats(e.take_stats(), [b for _, b in tb])
+            logs = self._logs_from_stats(self._take_stats(), [b for _, b in tb])
             vb = batches(n - split_at, True)
             if vb:
                 for s0, b in vb:
                     self._load_rows(xd, yd, rows_of(val_rows[s0:s0 + b], b), b)
                     e.eval_step()
-                vl = self._logs_from_stats(e.take_stats(), [b for _, b in vb])
+                vl = self._logs_from_stats(self._take_stats(), [b for _, b in vb])
                 for k, v in vl.items():
                     logs["val_" + k] = v
             for k, v in logs.items():
@@ -509,6 +530,9 @@ class Model(object):
                     if t is not None:
                         tensors["opt/b%d/%d" % (i, j)] = t.cpu().numpy()
             tensors["opt/iterations"] = np.array([self.optimizer.iterations], np.int64)
+        # the objective, with the optimizer state: a resumed run must not silently switch it
+        tensors["loss/name"] = np.frombuffer(self.loss.name.encode("ascii"), np.uint8).copy()
+        tensors["loss/param"] = np.array([self.loss.param], np.float64)
         save_file(tensors, path)
 
     def load(self, path, with_optimizer=True):
@@ -517,6 +541,11 @@ class Model(object):
         n = len([k for k in t if k.startswith("param/")])
         self.set_weights([t["param/%d" % i] for i in range(n)])
         e = self.engine
+        if with_optimizer:
+            # the objective saved with the optimizer state (a file from before the losses: the squared loss)
+            saved = self.saved_loss(t)
+            e.set_loss(saved)
+            self.loss = saved
         if with_optimizer and self.optimizer is not None and "opt/iterations" in t:
             for i, (sw, sb) in enumerate(e.slots):
                 for j, s in enumerate(sw):
@@ -526,6 +555,16 @@ class Model(object):
                     if s is not None:
                         s.copy_(torch.as_tensor(t["opt/b%d/%d" % (i, j)]))
             self.optimizer.iterations = int(t["opt/iterations"][0])
+
+
+    @staticmethod
+    def saved_loss(tensors):
+        """the losses.Loss a Model.save file holds (its load_file dict); files without one mean MSE"""
+        if "loss/name" not in tensors:
+            return losses.MeanSquaredError()
+        name = bytes(bytearray(tensors["loss/name"].astype(np.uint8))).decode("ascii")
+        param = float(tensors["loss/param"][0])
+        return losses.get(name, {"delta": param} if name == losses.Huber.name else None)
 
 
 class _Donor(object):

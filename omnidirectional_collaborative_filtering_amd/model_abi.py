@@ -25,10 +25,15 @@ def ptr(t):
 
 class ModelABI:
     def __init__(self, N, hidden, max_batch, k_blocks=1, activation="sigmoid", dropout=0.0,
-                 compute_dtype="float32", seed=0, optimizer=None, device="cuda"):
+                 compute_dtype="float32", seed=0, optimizer=None, device="cuda", loss="mean_squared_error",
+                 loss_params=None):
         if not torch.cuda.is_available():
             raise RuntimeError("ModelABI needs a ROCm GPU (MI355X)")
         _lib.load()
+        from . import losses
+        # the objective (losses.get: a name with loss_params, or a Loss): ocf_masked_mse for the squared loss,
+        # ocf_masked_loss for the others, and the matching gradient scale in backward
+        self.loss = losses.get(loss, loss_params)
         self.N, self.k, self.H, self.B_max = int(N), int(k_blocks), [int(h) for h in hidden], int(max_batch)
         self.dev = torch.device(device)
         d = _lib.OcfModelDesc()
@@ -127,6 +132,12 @@ class ModelABI:
         targets = targets if targets.stride(0) == self.N else targets.contiguous()
         out_mask = out_mask if out_mask is None or out_mask.stride(0) == self.N else out_mask.contiguous()
         self.grad = self._out("grad", B, self.N)
+        if self.loss.code != _lib.LOSS_MSE:
+            # ocf_masked_loss: the same layout plus the per-row sums of rho(e) [B]; stats[3] = sum rho / (B N)
+            self.stats = self._out("stats", 4 + 4 * B)
+            call("ocf_masked_loss", self.loss.code, self.loss.param, ptr(pred), ptr(targets), ptr(out_mask), self.N, B,
+                 self.N, ptr(self.grad), self.N, ptr(self.stats), s)
+            return self.grad, self.stats
         self.stats = self._out("stats", 4 + 3 * B)
         call("ocf_masked_mse", ptr(pred), ptr(targets), ptr(out_mask), self.N, B, self.N, ptr(self.grad), self.N,
              ptr(self.stats), s)
@@ -137,7 +148,7 @@ class ModelABI:
         n = len(self.W)
         gw = (ctypes.c_void_p * n)(*[ptr(g) for g in self.gW])
         gb = (ctypes.c_void_p * n)(*[ptr(g) for g in self.gb])
-        call("ocf_backward", self.ctx, ptr(grad), grad.stride(0), B, 2.0 / (B * self.N), gw, gb, s)
+        call("ocf_backward", self.ctx, ptr(grad), grad.stride(0), B, self.loss.grad_num / (B * self.N), gw, gb, s)
 
     def opt_step(self):
         s = torch.cuda.current_stream().cuda_stream
@@ -148,7 +159,7 @@ class ModelABI:
 
     def train_on_batch(self, inputs, out_mask, targets, masks_out=None):
         """train.py:157's per-batch step; returns this step's device stats (ocf_masked_mse layout) as a fresh
-        tensor (4 + 3 B floats), so a caller may keep per-step stats on the device and read them later.
+        tensor (4 + 3 B floats; 4 + 4 B under a loss other than MSE), so a caller may keep per-step stats on the device and read them later.
         forward / masked_mse return the model's reused output buffers instead (pred, grad, stats: the next
         call overwrites them)."""
         B = targets.shape[0]

@@ -40,6 +40,8 @@ DEFAULTS = dict(
     activation_type="sigmoid", use_sparse_representation=False, use_experimental_sparse_masking_layer=False,
     load_weights_from=None, perform_finetuning=False, compute_dtype="float32", metadata="./datasets_metadata.json",
     synthetic=None, seed=None, rng="numpy", parallel="feature", dp_mode="sharded", dp_grad_dtype="float32",
+    # model_loss (--loss): mean_squared_error | mean_absolute_error | huber | logcosh; huber_delta (--huber-delta)
+    huber_delta=1.0,
 )
 
 
@@ -158,7 +160,9 @@ def run(cfg):
     opt = {"adagrad": lambda: O.Adagrad(lr=cfg["learning_rate"], epsilon=1e-08, decay=0.0),
            "rmsprop": lambda: O.RMSprop(lr=cfg["learning_rate"]),
            "adam": lambda: O.Adam(lr=cfg["learning_rate"])}[cfg["optimizer"]]()
-    m.compile(opt, cfg["model_loss"], metrics=["mae", "accurate_MAE", "nMAE", "accurate_RMSE", "accurate_MSE"])
+    loss_name = str(cfg["model_loss"]).lower()
+    m.compile(opt, loss_name, loss_params={"delta": cfg.get("huber_delta", 1.0)} if loss_name == "huber" else None,
+              metrics=["mae", "accurate_MAE", "nMAE", "accurate_RMSE", "accurate_MSE"])
     if fp:
         m.enable_feature_parallel(rank, world)
     elif world > 1:
@@ -248,6 +252,10 @@ def main(argv=None):
             ap.add_argument("--" + k, type=lambda s: None if s in ("None", "none") else _num(s), default=None)
         else:
             ap.add_argument("--" + k, type=type(v), default=v)
+    ap.add_argument("--loss", dest="model_loss", type=str, default=argparse.SUPPRESS,
+                    help="the training loss (= --model_loss): mean_squared_error, mean_absolute_error, huber, logcosh")
+    ap.add_argument("--huber-delta", dest="huber_delta", type=float, default=argparse.SUPPRESS,
+                    help="the huber loss's delta (> 0)")
     cfg = vars(ap.parse_args(argv))
     return run(cfg)
 
