@@ -173,7 +173,7 @@ typedef struct OcfGatherArgs {
   const void* h; int h_dtype;                 /* [Bp][H] hidden activations (compute dtype)       */
   const float* bias; float aux;               /* output bias, output-mask value (train.py:47)     */
   float* delta_e;            /* per batch-local entry delta err*m (nullable)                      */
-  float* chunk_stats;        /* [n_chunks][4]: SSE, SAE, count_nonzero(T + yhat), 0 (see loss)    */
+  float* chunk_stats;        /* [n_chunks][4]: SSE, SAE, count_nonzero(T + yhat), - (see loss)    */
   void* d_out; int d_dtype; int64_t ld_d;     /* optional dense delta (zero elsewhere)            */
   /* decoder, optional (enc_part != NULL, one hidden layer): the hidden layer's bias / activation /
    * dropout applied here instead of by ocf_rows_reduce(OCF_REDUCE_BIAS_ACT) -- h[b] = dropout(act(the
@@ -192,9 +192,9 @@ typedef struct OcfGatherArgs {
    * and jr->chunk_stats must be this launch's part and chunk_stats, jr->H its H. */
   const struct OcfRowsReduceArgs* jr; uint32_t* row_arrive;
   /* decoder: the loss (OCF_LOSS_*, 0 = MSE) and its parameter.  Not MSE: chunk_stats[c][3] = the chunk's sum of
-   * rho(e); the folded row reduction (jr) writes the row's sum to jr->stats_part[b][3]; a separate ocf_rows_reduce
-   * needs its stats4 set; the reduction as a job of a weight-gradient launch (OcfGemmArgs jr) and ocf_rank_step
-   * are MSE only */
+   * rho(e) (MSE: that slot is not written); the folded row reduction (jr) writes the row's sum to
+   * jr->stats_part[b][3]; a separate ocf_rows_reduce needs its stats4 set; the reduction as a job of a
+   * weight-gradient launch (OcfGemmArgs jr) and ocf_rank_step are MSE only */
   int loss; float loss_param;
 } OcfGatherArgs;
 
