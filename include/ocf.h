@@ -221,7 +221,13 @@ int ocf_gather_encdec(const OcfGatherArgs* enc, const OcfGatherArgs* dec, uint32
  * per 256 batch rows (the row gathers read a W1 row per entry) and multiplied by the batch's X tile, densified in
  * LDS from the rows' column-sorted entries.  Writes split-K partials part[b][s][h] (s < splits: contiguous tile
  * ranges); the caller sums them with ocf_rows_reduce (row_cptr[b] = b * splits).  X = the live input values
- * (xval, list order; duplicates added) rounded to the compute dtype; fp32 accumulation. */
+ * (xval, list order; duplicates added) rounded to the compute dtype; fp32 accumulation.
+ * Duplicates (a run of entries of one row in one column): the packed form ("enc_tiles_pack" 1) adds the run's
+ * values in fp32 and rounds the sum once; the per-row form adds them one by one in the compute dtype.  The two
+ * agree whenever at most one value of a run is nonzero, which is all ocf_epoch_scatter produces (the earlier
+ * entries of a chain are 0), and whenever every partial sum is exact in the compute dtype.
+ * W: every row below n_tiles * 128 is read and multiplied, the rows at or beyond the real column count by X zeros,
+ * so all of them must be finite (0 * NaN = NaN); the columns at or beyond H (ldw > H) are never read. */
 typedef struct OcfEncTileArgs {
   const int32_t* rows;    /* [B] dataset row per batch row (-1 = none)                                      */
   const int64_t* rp;      /* row pointers of the dataset CSR                                                */
