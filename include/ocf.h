@@ -801,6 +801,20 @@ int ocf_backward(OcfCtx* ctx, const float* grad, int64_t ld_grad, int B, float g
  * compute-dtype copy of W[i] rewritten by the update (64 x 64-blocked with shadow_blocked).  l2 = 0.
  * stats: {sse, sae, count_nonzero(T + y), 0, row sse [Bp]} (the masked-MSE statistics).  work: scratch of
  * ocf_mlp_step_workspace bytes.  barrier: device uint32[2], zero before the first launch, left reusable.
+ * What tests/test_mlp_direct_gpu.py pins down:
+ *  - opt.kind 0 (SGD, no slots) is accepted beside Adagrad / RMSprop / Adam (sW1 / sb1, Adam also sW2 / sb2).
+ *  - rows may repeat and need no order (rows[b] is read for b < B only); the source arrays may be taller than the
+ *    batch; ld_x and ld_t are independent (each >= N), no column at or beyond N is read.
+ *  - mask[i] is written for all Bp x hidden_p[i] elements (padding rows and units included); nothing else of the
+ *    caller's is written beside W, b, the slots, shadow and stats.
+ *  - stats needs 4 + Bp floats; nothing beyond them is written.
+ *  - the results (every parameter, slot, shadow, statistic) do not depend on wgs, bit for bit: every sum has a fixed
+ *    order.  Nor do they depend on what the workspace held before the launch.
+ *  - padding: W's padded rows / columns must hold finite values (they meet zero operands, 0 x NaN would spread);
+ *    the padding of sW1 / sW2 must be zero (the update runs over every element of W with a zero gradient there,
+ *    which leaves W and a zero slot bit-unchanged under every optimizer; a nonzero slot would decay); shadow's
+ *    padding is rewritten with the rounding of W's; the padding of b, sb1, sb2 is neither read into a result nor
+ *    written.
  */
 typedef struct OcfMlpStepArgs {
   int n_hidden;                                   /* L, 1..OCF_MAX_HIDDEN */
