@@ -451,6 +451,44 @@ int64_t ocf_topk_workspace(const OcfTopkArgs* args);
 int ocf_topk(const OcfTopkArgs* args, void* stream);
 
 /*
+ * ocf_predict_entries -- the decoder's prediction at listed entries only (csrc/ocf_predict.hip): for every batch
+ * row b < B with rows[b] >= 0 and every entry j of row rows[b] of a query CSR (rp, col, nullable val)
+ *   y[lboff[b] + j] = clip( aux * ( sum_x h[b][x] * W[col][x] + bias[col] ) )
+ * in fp32, without the decoder GEMM over all columns and without a [B][N] array: one weight row is read per entry.
+ * It is the forward half of ocf_gather_decoder (the same lane groups and 16-byte row pieces, so the blocked shadow
+ * is read as it lies) without the hidden-delta sums, their partials and the arrival counters; every entry is
+ * independent, so y does not depend on the chunk tables.  A zero-initialised struct means no clipping and no
+ * statistics.  Two launches at most, no atomics, no wait between workgroups.
+ * Chunk tables: as OcfGatherArgs' (batch row and local entry range per chunk), chunks of any length; the chunks of
+ * a batch row are consecutive and ch_row is non-decreasing (BatchGenerator._chunk_tables builds them so): the
+ * second launch finds a row's chunks by a search of ch_row.
+ * Statistics (val and row_stats both set): over the row's flagged entries (all entries when flag is null), on the
+ * stored (clipped) y and the target t = val: row_stats[b] = {sum (y - t)^2, sum |y - t|, count_nonzero(t + y), 0},
+ * the chunk rows of chunk_stats added in chunk order by a second small launch (deterministic); rows without entries
+ * and the padding rows B <= b < Bp get zeros; total = the rows added in a fixed order.
+ */
+typedef struct OcfPredictArgs {
+  const int32_t* rows;       /* [B] CSR row of each batch row (-1 = none)                                    */
+  const int64_t* rp; const int32_t* col; const float* val;   /* the query CSR; val nullable (no statistics) */
+  const int64_t* lboff;      /* [B+1] batch-local entry offsets: the index of y and flag                     */
+  const uint8_t* flag;       /* nullable: per batch-local entry, 0 = left out of the statistics (y is written) */
+  const int32_t* ch_row; const int32_t* ch_j0; const int32_t* ch_j1;
+  int n_chunks;
+  int B, Bp;                 /* real batch rows; rows of h, row_stats (>= B)                                 */
+  const void* h; int h_dtype; int64_t ldh;      /* [Bp][ldh] last hidden activations, OCF_DT_*               */
+  int H;                     /* padded hidden width: a multiple of 128 in [128, 2048]                        */
+  const void* W; int w_dtype; int64_t ldw; int w_blocked;   /* [Np][ldw] decoder weight, one row per column:
+                                fp32 master or 16-bit shadow, row-major or 64x64-blocked (16-bit only)       */
+  const float* bias; float aux;                 /* [Np] output bias; the output-mask value                   */
+  int clip; float clip_lo, clip_hi;             /* clip != 0: y = min(max(y, clip_lo), clip_hi)              */
+  float* y;                  /* fp32 per batch-local entry: written at every entry, nothing else of it       */
+  float* chunk_stats;        /* [n_chunks][4] scratch (statistics only)                                      */
+  float* row_stats;          /* [Bp][4], nullable                                                            */
+  float* total;              /* [4] the sum of the rows                                                      */
+} OcfPredictArgs;
+int ocf_predict_entries(const OcfPredictArgs* args, void* stream);
+
+/*
  * ocf_gemm_pair -- ocf_gemm(a) then ocf_gemm(b) for the two weight updates of a one-hidden-layer step
  * (a = the output layer, with the decoder's folded row reduction jr; b = the input layer, whose operand B
  * and job inputs that reduction writes: train.py:50-51 for both kernels).  When both take the row-stream

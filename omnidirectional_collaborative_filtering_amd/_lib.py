@@ -150,6 +150,18 @@ class OcfTopkArgs(ctypes.Structure):
     ]
 
 
+class OcfPredictArgs(ctypes.Structure):
+    """ocf.h OcfPredictArgs: the decoder's prediction at listed entries (ocf_predict_entries)"""
+    _fields_ = [
+        ("rows", P), ("rp", P), ("col", P), ("val", P), ("lboff", P), ("flag", P),
+        ("ch_row", P), ("ch_j0", P), ("ch_j1", P), ("n_chunks", I32), ("B", I32), ("Bp", I32),
+        ("h", P), ("h_dtype", I32), ("ldh", I64), ("H", I32),
+        ("W", P), ("w_dtype", I32), ("ldw", I64), ("w_blocked", I32),
+        ("bias", P), ("aux", F32), ("clip", I32), ("clip_lo", F32), ("clip_hi", F32),
+        ("y", P), ("chunk_stats", P), ("row_stats", P), ("total", P),
+    ]
+
+
 class OcfPairSync(ctypes.Structure):
     """ocf.h OcfPairSync: ocf_gemm_pair's hand-off counter (device word + its host-side running count)"""
     _fields_ = [("word", P), ("count", U64)]
@@ -258,6 +270,7 @@ SIGNATURES = {
     "ocf_gemm": (I32, [ctypes.POINTER(OcfGemmArgs), P]),
     "ocf_topk": (I32, [ctypes.POINTER(OcfTopkArgs), P]),
     "ocf_topk_workspace": (I64, [ctypes.POINTER(OcfTopkArgs)]),
+    "ocf_predict_entries": (I32, [ctypes.POINTER(OcfPredictArgs), P]),
     "ocf_gemm_pair": (I32, [ctypes.POINTER(OcfGemmArgs), ctypes.POINTER(OcfGemmArgs), P, P]),   # P: OcfPairSync*
     "ocf_train_step_rows": (I32, [ctypes.POINTER(OcfRowStepArgs), P]),
     "ocf_rank_step": (I32, [ctypes.POINTER(OcfRankStepArgs), I32, P]),

@@ -169,13 +169,15 @@ class RatingsCSR:
     @classmethod
     def from_coo(cls, rows, cols, vals, n_rows, keys=None, dup_free=False):
         """rows need not be sorted; within a row the given order is kept (stable).  dup_free: the
-        caller guarantees unique (row, col) pairs (no duplicate chain to build)."""
+        caller guarantees unique (row, col) pairs (no duplicate chain to build).  vals may be None: a list of
+        positions without ratings (Model.predict_entries' queries)."""
         rows = np.asarray(rows, dtype=np.int64)
         order = stable_order(rows)
         counts = np.bincount(rows, minlength=n_rows)
         rp = np.zeros(n_rows + 1, dtype=np.int64)
         np.cumsum(counts, out=rp[1:])
-        c = cls(rp, np.asarray(cols, dtype=np.int32)[order], np.asarray(vals, dtype=np.float32)[order],
+        c = cls(rp, np.asarray(cols, dtype=np.int32)[order],
+                None if vals is None else np.asarray(vals, dtype=np.float32)[order],
                 list(range(n_rows)) if keys is None else list(keys))
         c.dup = None if dup_free else dup_chain(rp, c.col)
         return c

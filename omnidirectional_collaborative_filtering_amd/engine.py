@@ -1260,6 +1260,54 @@ class Engine:
         del keep
         return (idx, val) if rank is None else (idx, val, rank)
 
+    # ---------------------------------------------------------------- per-entry predictions (ocf_predict_entries)
+    def predict_entries(self, query, clip=None, stats=True):
+        """The decoder's prediction at the entries of a query CSR (ocf_predict_entries), after
+        forward(training=False): y[lboff[b] + j] = clip(aux * (h[b] . W_out[col] + b_out[col])) for every entry j of
+        row rows[b] of the CSR -- one decoder weight row read per entry, no decoder GEMM, no [B, N] array.
+
+        query: dict of device tensors or raw pointers rows [B] int32, rp, col, val (None: no statistics), lboff
+        [B + 1] int64, flag (uint8 per batch-local entry or None), ch_row / ch_j0 / ch_j1 and the ints n_chunks, E
+        (the batch's entry count), plus aux (the output-mask value, default 1): BatchGenerator.gather_tables' form.
+        clip: (lo, hi) or None.  stats: False skips the statistics even when val is given.
+        Returns (y [E] fp32, row_stats [B, 4] or None, total [4] or None) as device tensors; row_stats[b] =
+        {sum (y - t)^2, sum |y - t|, count_nonzero(t + y), 0} over the row's flagged entries, on the clipped y.
+
+        Nothing of the training state changes: no stats row, no step count, dropout off.  The scratch is the
+        engine's own tensor, outside the buffers whose growth invalidates the one-call step's plan."""
+        if self.comm is not None:
+            raise ValueError("predict_entries: a feature-parallel engine holds a column shard; per-shard predictions "
+                             "are not built")
+        if self.master_sync is not None:
+            self.master_sync()
+        self._finish_deferred_encoder()
+        L = len(self.H)
+        Wt, wdt = self._wop(L)
+        a = _lib.OcfPredictArgs()
+        for k in ("rows", "rp", "col", "val", "lboff", "flag", "ch_row", "ch_j0", "ch_j1"):
+            v = query.get(k)
+            setattr(a, k, v.data_ptr() if torch.is_tensor(v) else v)
+        a.n_chunks, E = int(query["n_chunks"]), int(query["E"])
+        a.B, a.Bp = self.B, self.Bp
+        a.h, a.h_dtype, a.ldh, a.H = ptr(self.h[L - 1]), self.cdt, self.Hp[L - 1], self.Hp[L - 1]
+        a.W, a.w_dtype, a.ldw, a.w_blocked = ptr(Wt), wdt, Wt.shape[1], self._wblk(L)
+        a.bias, a.aux = ptr(self.b[L]), float(query.get("aux", 1.0))
+        if clip is not None:
+            lo, hi = float(clip[0]), float(clip[1])
+            a.clip, a.clip_lo, a.clip_hi = 1, lo, hi
+        y = torch.empty(max(E, 1), device=self.dev, dtype=torch.float32)
+        a.y = ptr(y)
+        rows = total = None
+        if stats and a.val:
+            w = getattr(self, "_pred_work", None)
+            if w is None or w.numel() < 4 * a.n_chunks:
+                w = self._pred_work = torch.empty(max(4 * a.n_chunks, 1024), device=self.dev, dtype=torch.float32)
+            rows = torch.empty(self.Bp, 4, device=self.dev, dtype=torch.float32)
+            total = torch.empty(4, device=self.dev, dtype=torch.float32)
+            a.chunk_stats, a.row_stats, a.total = ptr(w), ptr(rows), ptr(total)
+        call("ocf_predict_entries", a, cur_stream())
+        return y[:E], (None if rows is None else rows[: self.B]), total
+
     # ---------------------------------------------------------------- per-column top-K (the transposed ocf_topk)
     def encode_rows(self, gen):
         """The last hidden activations of every row of a catalogue generator (data_reader.catalogue_gen: the

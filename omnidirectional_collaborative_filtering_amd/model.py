@@ -289,6 +289,104 @@ class Model(object):
         e.predict_dense(om, out)
         return out
 
+    def predict_entries(self, generator, steps, queries=None, clip=None):
+        """The predictions themselves at listed entries of `steps` generator batches (engine.Engine.predict_entries:
+        one decoder weight row read per entry, no dense [B, N] input, mask or output anywhere).
+
+        queries=None: a valid or test generator; the entries are those of the split's target CSR at the batch rows
+        whose live-target flag is set -- the set evaluate_sse counts.  queries = a dataset.RatingsCSR with as many
+        rows as the generator's input CSR (row i = the same dataset row; RatingsCSR.from_coo, values optional):
+        every entry of it is predicted, with any generator; statistics only if it carries values.
+        clip: (lo, hi) or None; the statistics are taken on the clipped predictions.
+
+        Returns a dict: rows (int64 dataset row per entry), cols (int32), targets (fp32 or None), predictions (fp32)
+        as CUDA tensors, in batch order, then batch-row order, then the CSR's list order; sse, sae, count (floats
+        from the device totals; None without targets) and rmse = sqrt(sse / entries).
+        Collective under data parallelism with ZeRO-1, like predict.  The generator advances as it does under
+        evaluate_generator; nothing of the training state changes."""
+        if not isinstance(generator, BatchGenerator):
+            raise ValueError("predict_entries takes a data_reader.data_gen generator (dense batches: predict)")
+        if queries is None and generator.split == "train":
+            raise ValueError("predict_entries needs a valid or test generator (a train generator has no held-out "
+                             "entries), or a queries CSR")
+        if clip is not None and not float(clip[0]) <= float(clip[1]):
+            raise ValueError("predict_entries: clip = (lo, hi) with lo <= hi")
+        e, gen, B = self.engine, generator, generator.B
+        self._check_gen(gen)
+        dev = e.dev
+        qt = None
+        out = dict(rows=[], cols=[], targets=[], predictions=[], flags=[])
+        totals = []
+        for _ in range(int(steps)):
+            bi = gen.next_batch_index()
+            if bi is None:
+                raise StopIteration("generator exhausted (data_reader.py:418 yields None)")
+            self._load(None, gen, bi)
+            e.forward(training=False)
+            rows_b = gen.rows_dev.view(-1)[bi * B:(bi + 1) * B]
+            if queries is None:
+                tab, src = gen.gather_tables(bi)["dec"], gen.src2
+                rp, col, val = src.rp, src.col, src.val
+                lb = gen.lboff2_dev[bi]
+                E = int(gen.tlocal[bi])
+                q = dict(tab, flag=e.tflag, aux=gen.aux, E=E)
+            else:
+                if qt is None:
+                    qt = self._query_tables(gen, queries)
+                rp, col, val = qt["rp"], qt["col"], qt["val"]
+                lb = qt["lboff"][bi]
+                E = int(qt["E"][bi])
+                ch = qt["chunks"]
+                c0 = int(ch["cbase"][bi])
+                q = dict(rows=rows_b, rp=rp, col=col, val=val, lboff=lb, flag=None, aux=gen.aux, E=E,
+                         ch_row=ch["ch_row"].data_ptr() + 4 * c0, ch_j0=ch["ch_j0"].data_ptr() + 4 * c0,
+                         ch_j1=ch["ch_j1"].data_ptr() + 4 * c0, n_chunks=int(ch["cbase"][bi + 1]) - c0)
+            y, _, total = e.predict_entries(q, clip=clip)
+            # (dataset row, column, target) of every batch-local entry, on the device
+            eb = torch.repeat_interleave(torch.arange(B, device=dev), lb[1:] - lb[:-1], output_size=E)
+            r = rows_b[eb].to(torch.int64)
+            pos = rp[r] + (torch.arange(E, device=dev) - lb[eb])
+            out["rows"].append(r)
+            out["cols"].append(col[pos])
+            out["predictions"].append(y)
+            if val is not None:
+                out["targets"].append(val[pos])
+                totals.append(total)
+            if queries is None:
+                out["flags"].append(e.tflag[:E].clone())
+        cat = lambda xs, dt: torch.cat(xs) if xs else torch.zeros(0, device=dev, dtype=dt)
+        res = dict(rows=cat(out["rows"], torch.int64), cols=cat(out["cols"], torch.int32),
+                   predictions=cat(out["predictions"], torch.float32),
+                   targets=cat(out["targets"], torch.float32) if (queries is None or queries.val is not None) else None)
+        if queries is None:                # the kernel writes every entry; the entries that are no live target leave
+            live = cat(out["flags"], torch.uint8) != 0
+            for k in ("rows", "cols", "predictions", "targets"):
+                res[k] = res[k][live]
+        res.update(sse=None, sae=None, count=None, rmse=None)
+        if res["targets"] is not None:
+            t = torch.stack(totals).double().sum(0).tolist() if totals else [0.0, 0.0, 0.0, 0.0]
+            n = int(res["predictions"].numel())
+            res.update(sse=float(t[0]), sae=float(t[1]), count=float(t[2]),
+                       rmse=float(np.sqrt(t[0] / n)) if n else float("nan"))
+        return res
+
+    def _query_tables(self, gen, queries):
+        """a queries CSR on the device with the batch-local offsets and chunk tables of the generator's epoch plan"""
+        src1 = gen.src1.host
+        if queries.n_rows != src1.n_rows:
+            raise ValueError("predict_entries: queries has %d rows, the generator's input CSR %d (row i is the same "
+                             "dataset row)" % (queries.n_rows, src1.n_rows))
+        e = self.engine
+        if queries.nnz and (int(queries.col.min()) < 0 or int(queries.col.max()) >= e.N):
+            raise ValueError("predict_entries: a queries column lies outside [0, %d)" % e.N)
+        dev = e.dev
+        lens = queries.row_lengths()
+        lboff = BatchGenerator._local_offsets(lens, gen.rows_host)
+        return dict(rp=torch.as_tensor(queries.row_ptr, device=dev), col=torch.as_tensor(queries.col, device=dev),
+                    val=None if queries.val is None else torch.as_tensor(queries.val, device=dev),
+                    lboff=torch.as_tensor(lboff, device=dev), E=lboff[:, -1],
+                    chunks=BatchGenerator._chunk_tables(lens, gen.rows_host, dev))
+
     # ------------------------------------------------------------------ recommendations (engine.Engine.topk)
     # The k best columns of every batch row straight from the decoder GEMM (ocf.h ocf_topk): no [B, N] score
     # matrix is written, the scores are bit-identical to predict's with an all-ones output mask, ordered by

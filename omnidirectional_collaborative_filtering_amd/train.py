@@ -42,6 +42,9 @@ DEFAULTS = dict(
     synthetic=None, seed=None, rng="numpy", parallel="feature", dp_mode="sharded", dp_grad_dtype="float32",
     # model_loss (--loss): mean_squared_error | mean_absolute_error | huber | logcosh; huber_delta (--huber-delta)
     huber_delta=1.0,
+    # save_test_predictions: path of an .npz with the test split's (row_keys, cols, ratings, predictions), written by
+    # rank 0 after the manual test leg (Model.predict_entries); clip_predictions: [lo, hi] clips them to the rating range
+    save_test_predictions=None, clip_predictions=None,
 )
 
 
@@ -117,6 +120,11 @@ def run(cfg):
     if seed is not None:
         np.random.seed(seed)
     fp = world > 1 and cfg["parallel"] == "feature"
+    save_pred, clip_pred = cfg.get("save_test_predictions"), cfg.get("clip_predictions")
+    if save_pred and fp:
+        raise ValueError("save_test_predictions: per-shard predictions are not built for --parallel feature")
+    if clip_pred is not None and not (len(clip_pred) == 2 and float(clip_pred[0]) <= float(clip_pred[1])):
+        raise ValueError("clip_predictions must be [lo, hi] with lo <= hi")
     if world > 1 and cfg["parallel"] not in ("feature", "dp"):
         raise ValueError("--parallel must be feature or dp")
     # dataset parameters (train.py:62-76)
@@ -226,8 +234,11 @@ def run(cfg):
     test_results = test_results if isinstance(test_results, list) else [test_results]
     out = {"test_" + k: v for k, v in zip(m.metrics_names, test_results)}
     manual = reader.data_gen(B, None, "test", cfg["shuffle_data_every_epoch"], aux, auxv, return_target_count=True)
+    rng_state = np.random.get_state() if save_pred else None     # the manual leg's permutation is drawn at its first pull
     sse, count = m.evaluate_sse(manual, int(np.floor(reader.test_set_size / B)))
     out["manual_test_RMSE"] = float(np.sqrt(sse / count)) if count else float("nan")
+    if save_pred:
+        out.update(_test_predictions(m, reader, cfg, rng_state, rank))
     out["best_epoch"] = best_epoch + 1
     out["epochs_run"] = i + 1
     out["val_history"] = list(stopper.val_history)
@@ -239,6 +250,33 @@ def run(cfg):
             if k != "manual_test_rows":
                 print(k, " : ", v)
     return out
+
+
+def _test_predictions(m, reader, cfg, rng_state, rank):
+    """The "Testing manually" leg with the predictions kept (train.py:225-255 of the reference): the batches of the
+    manual leg again (the same permutation: NumPy's state from before that leg, put back afterwards), predicted per
+    entry; rank 0 writes them.  With clip_predictions a second pass gives the clipped predictions and their RMSE."""
+    B, aux, auxv = cfg["batch_size"], cfg["auxilliary_mask_type"], cfg["aux_var_value"]
+    steps = int(np.floor(reader.test_set_size / B))
+    clip = cfg.get("clip_predictions")
+    after = np.random.get_state()
+    res = {}
+    for key, c in [("predicted_test_RMSE", None)] + ([("clipped_test_RMSE", tuple(clip))] if clip is not None else []):
+        np.random.set_state(rng_state)
+        gen = reader.data_gen(B, None, "test", cfg["shuffle_data_every_epoch"], aux, auxv)
+        p = m.predict_entries(gen, steps, clip=c)
+        res[key] = p["rmse"]
+    np.random.set_state(after)
+    if rank == 0:
+        keys = np.asarray(reader.data.test_tgt.keys)
+        path = cfg["save_test_predictions"]
+        d = os.path.dirname(path)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        with open(path, "wb") as f:
+            np.savez(f, row_keys=keys[p["rows"].cpu().numpy()], cols=p["cols"].cpu().numpy(),
+                     ratings=p["targets"].cpu().numpy(), predictions=p["predictions"].cpu().numpy())
+    return res
 
 
 def main(argv=None):
@@ -261,6 +299,8 @@ def main(argv=None):
 
 
 def _num(s):
+    if s.startswith("["):              # a list-valued option whose default is None (--clip_predictions "[0.5, 5]")
+        return json.loads(s)
     for t in (int, float):
         try:
             return t(s)
