@@ -36,6 +36,8 @@ extern "C" {
 #define OCF_OPTK_ADAGRAD 1
 #define OCF_OPTK_RMSPROP 2
 #define OCF_OPTK_ADAM 3
+#define OCF_OPTK_ADADELTA 4 /* s1 = a (mean of g^2), s2 = d (mean of squared updates); rho */
+#define OCF_OPTK_ADAMAX 5   /* s1 = m, s2 = u (infinity norm); lr = lr_t, rho = beta_1, beta2 = beta_2 */
 
 /* training losses: rho applied to the residual e = m * y - t of every live target entry (rho(0) = 0, so the Keras
  * mean over all B * N elements is a sum over the live entries).  loss_param: Huber's delta (> 0), ignored by the
@@ -611,8 +613,10 @@ int ocf_splitk_grad_act(const float* slabs, int splits, int64_t split_stride, in
                         const float* a_in, const uint8_t* mask, float keep, int act, void* d_out, int d_dtype,
                         float* db, float gscale, int m_real, int n_real, void* hstream);
 
-/* ocf_opt_step -- elementwise Adagrad / RMSprop / Adam / SGD update (Keras 2.0.4 get_updates);
- * g is multiplied by opt.gscale.  Used for biases and after the data-parallel all-reduce. */
+/* ocf_opt_step -- elementwise SGD / Adagrad / RMSprop / Adam / Adadelta / Adamax update (Keras 2.0.4
+ * get_updates); g is multiplied by opt.gscale.  Used for biases and after the data-parallel all-reduce.
+ * Adadelta and Adamax need both slots (s1 and s2 non-null); a kind outside OCF_OPTK_* is an error (as in
+ * ocf_opt_step_ex, ocf_bias_opt_from_partials, ocf_gemm's OCF_EPI_OPTIM and ocf_mlp_step). */
 int ocf_opt_step(float* p, const float* g, float* s1, float* s2, int64_t n, const OcfOptParams* opt, void* stream);
 /* ocf_opt_step_ex -- ocf_opt_step on a gradient in fp32 or bf16 (g_dtype OCF_F32 / OCF_BF16: a
  * data-parallel reduce-scatter shard as it arrives), optionally writing the updated parameter rounded

@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("OCF_LIB_PATH") or os.path.join(_HERE, "libocf.so")   
 
 DT_F32, DT_F16, DT_BF16 = 0, 1, 2
 ACT = {"linear": 0, None: 0, "sigmoid": 1, "tanh": 2, "relu": 3}
-OPT_SGD, OPT_ADAGRAD, OPT_RMSPROP, OPT_ADAM = 0, 1, 2, 3
+OPT_SGD, OPT_ADAGRAD, OPT_RMSPROP, OPT_ADAM, OPT_ADADELTA, OPT_ADAMAX = 0, 1, 2, 3, 4, 5
 LIVE_REC = 144                 # ocf.h OCF_LIVE_REC
 EPI_SLAB, EPI_BIAS_ACT, EPI_GRAD_ACT, EPI_GRAD, EPI_OPTIM, EPI_PREDICT, EPI_MASKED_MSE = range(7)
 LOSS_MSE, LOSS_MAE, LOSS_HUBER, LOSS_LOGCOSH = range(4)     # ocf.h OCF_LOSS_*

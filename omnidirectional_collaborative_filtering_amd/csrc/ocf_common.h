@@ -32,6 +32,8 @@ enum {
   OCF_OPT_ADAGRAD = 1,
   OCF_OPT_RMSPROP = 2,
   OCF_OPT_ADAM = 3,
+  OCF_OPT_ADADELTA = 4,   // Keras 2.0.4 Adadelta (s1 = a, s2 = d)
+  OCF_OPT_ADAMAX = 5,     // Keras 2.0.4 Adamax (s1 = m, s2 = u)
 };
 
 

@@ -363,6 +363,7 @@ extern "C" int ocf_opt_step(float* p, const float* g, float* s1, float* s2, int6
                             void* stream) {
   OCF_TRY_BEGIN
   OCF_CHECK(p && g && opt, "ocf_opt_step: null pointer");
+  check_opt(*opt, s1, s2, "ocf_opt_step");
   if (n == 0) return 0;
   int64_t blocks = (n + 255) / 256;
   if (blocks > 8192) blocks = 8192;
@@ -377,6 +378,7 @@ extern "C" int ocf_opt_step_ex(const OcfOptStepArgs* a, void* stream) {
   OCF_CHECK(a->g_dtype == OCF_F32 || a->g_dtype == OCF_BF16, "ocf_opt_step_ex: gradients fp32 or bf16");
   OCF_CHECK(!a->shadow || a->shadow_dtype == OCF_F16 || a->shadow_dtype == OCF_BF16,
             "ocf_opt_step_ex: shadow f16 or bf16");
+  check_opt(a->opt, a->s1, a->s2, "ocf_opt_step_ex");
   if (a->n == 0) return 0;
   int64_t blocks = (a->n + 255) / 256;
   if (blocks > 8192) blocks = 8192;
@@ -399,6 +401,7 @@ extern "C" int ocf_bias_opt_from_partials(float* b, const float* db_part, int pa
                                           float* s2, float* g_out, const OcfOptParams* opt, void* stream) {
   OCF_TRY_BEGIN
   OCF_CHECK(b && db_part && opt, "ocf_bias_opt_from_partials: null pointer");
+  if (!g_out) check_opt(*opt, s1, s2, "ocf_bias_opt_from_partials");   // (g_out: the gradient only, no update)
   if (n == 0) return 0;
   hipLaunchKernelGGL(bias_opt_partials_kernel, dim3((n + 63) / 64), dim3(256), 0, (hipStream_t)stream, b, db_part,
                      parts, ld, n, s1, s2, g_out, *opt);

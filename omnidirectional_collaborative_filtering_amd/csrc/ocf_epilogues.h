@@ -32,8 +32,36 @@ __device__ __forceinline__ void for_each_acc(ocf_f16v (&acc)[2][2], const TileCt
 // ---- optimizer update (Keras 2.0.4 get_updates, float32 op order) ---------------------
 // KIND fixed at compile time where a kernel is specialised per optimizer (optim_ws_kernel: a
 // quarter of the code of the runtime switch below, which matters for the instruction cache)
+// slot arrays a kind keeps per parameter: 0 SGD, 1 Adagrad / RMSprop (s1), 2 Adam / Adadelta / Adamax (s1, s2);
+// -1 for a value outside the OCF_OPT_* enum.  The kernels size their slot streams by it.
+__host__ __device__ constexpr int opt_slots(int kind) {
+  return kind == OCF_OPT_SGD ? 0
+         : (kind == OCF_OPT_ADAGRAD || kind == OCF_OPT_RMSPROP) ? 1
+         : (kind == OCF_OPT_ADAM || kind == OCF_OPT_ADADELTA || kind == OCF_OPT_ADAMAX) ? 2
+                                                                                         : -1;
+}
+// an entry point's optimizer arguments: a kind of the enum; Adadelta / Adamax with both slots (the kinds before
+// them keep their present routes, whatever slots they are given)
+inline void check_opt(const OcfOptParams& o, const void* s1, const void* s2, const char* who) {
+  if (opt_slots(o.kind) < 0)
+    throw std::runtime_error(std::string(who) + ": unknown optimizer kind " + std::to_string(o.kind) +
+                             " (OCF_OPTK_* 0..5)");
+  if ((o.kind == OCF_OPT_ADADELTA || o.kind == OCF_OPT_ADAMAX) && !(s1 && s2))
+    throw std::runtime_error(std::string(who) + ": Adadelta / Adamax need both optimizer slots (s1, s2)");
+}
+
+// fp32 operation order (the build has -ffp-contract=off, so this is what runs; tests/optim_ref.py restates it):
+//   every kind   g  = g + (2*l2)*p                      when l2 != 0
+//   Adadelta     a' = rho*a + (1-rho)*(g*g)
+//                u  = (g * sqrt(d + eps)) / sqrt(a' + eps)
+//                p' = p - lr*u
+//                d' = rho*d + (1-rho)*(u*u)
+//   Adamax       m' = rho*m + (1-rho)*g                 (rho = beta_1)
+//                u' = max(beta2*u, |g|)
+//                p' = p - (lr*m') / (u' + eps)          (lr = lr_t = lr / (1 - beta_1^t), from the host)
 template <int KIND>
 __device__ __forceinline__ void opt_update_k(const OcfOptParams& o, float g, float& p, float& s1, float& s2) {
+  static_assert(opt_slots(KIND) >= 0, "optimizer kind");
   if (o.l2 != 0.f) g = g + 2.0f * o.l2 * p;
   if constexpr (KIND == OCF_OPT_ADAGRAD) {        // a += g^2 ; p -= lr*g/(sqrt(a)+eps)
     float a = s1 + g * g;
@@ -49,6 +77,18 @@ __device__ __forceinline__ void opt_update_k(const OcfOptParams& o, float g, flo
     s1 = m;
     s2 = v;
     p = p - (o.lr * m) / (sqrtf(v) + o.eps);
+  } else if constexpr (KIND == OCF_OPT_ADADELTA) {  // a, d EMAs of g^2 and u^2; p -= lr*u
+    float a = o.rho * s1 + (1.0f - o.rho) * (g * g);
+    float u = (g * sqrtf(s2 + o.eps)) / sqrtf(a + o.eps);
+    s1 = a;
+    p = p - o.lr * u;
+    s2 = o.rho * s2 + (1.0f - o.rho) * (u * u);
+  } else if constexpr (KIND == OCF_OPT_ADAMAX) {    // m EMA, u infinity norm; p -= lr_t*m/(u+eps)
+    float m = o.rho * s1 + (1.0f - o.rho) * g;
+    float u = fmaxf(o.beta2 * s2, fabsf(g));
+    s1 = m;
+    s2 = u;
+    p = p - (o.lr * m) / (u + o.eps);
   } else {
     (void)s1; (void)s2;
     p = p - o.lr * g;
@@ -59,7 +99,9 @@ __device__ __forceinline__ void opt_update(const OcfOptParams& o, float g, float
     case OCF_OPT_ADAGRAD: opt_update_k<OCF_OPT_ADAGRAD>(o, g, p, s1, s2); break;
     case OCF_OPT_RMSPROP: opt_update_k<OCF_OPT_RMSPROP>(o, g, p, s1, s2); break;
     case OCF_OPT_ADAM: opt_update_k<OCF_OPT_ADAM>(o, g, p, s1, s2); break;
-    default: opt_update_k<0>(o, g, p, s1, s2);
+    case OCF_OPT_ADADELTA: opt_update_k<OCF_OPT_ADADELTA>(o, g, p, s1, s2); break;
+    case OCF_OPT_ADAMAX: opt_update_k<OCF_OPT_ADAMAX>(o, g, p, s1, s2); break;
+    default: opt_update_k<0>(o, g, p, s1, s2);   // SGD (the entry points refuse a kind outside the enum)
   }
 }
 

@@ -52,6 +52,7 @@ void launch(const OcfGemmArgs& g, const typename Epi::Params& ep, hipStream_t s)
 // (dW 132 / 111 us vs 175 / 137 us).
 int g_optim_ws = 1;      // role-split kernel for dense-A EPI_OPTIM (ocf_set_tuning "optim_ws")
 int g_optim_ws_max_k = 512;   // K = 512 (2-way feature parallel): 0.453 vs 0.509 ms/step on the generic kernel; K = 1,024: 0.42 vs 0.38
+int g_optim_ws_count = 0;   // role-split launches since the last read ("optim_ws_count": tests see which kernel ran)
 bool optim_ws_on() { return g_optim_ws != 0; }
 
 
@@ -98,11 +99,21 @@ void launch_ws(const OcfGemmArgs& g, const EpiOptim::Params& ep, hipStream_t s) 
     case OCF_OPT_RMSPROP:
       hipLaunchKernelGGL((optim_ws_kernel<CT, SPA, OCF_OPT_RMSPROP>), dim3(G), dim3(WS_THREADS), 0, s, sh, ep, jb);
       break;
-    default:
-      OCF_CHECK(g.opt.kind == OCF_OPT_ADAM && g.s2, "optim_ws: Adagrad, RMSprop or Adam (with both slots)");
+    case OCF_OPT_ADAM:
+      OCF_CHECK(g.s2, "optim_ws: Adam needs both slots");
       hipLaunchKernelGGL((optim_ws_kernel<CT, SPA, OCF_OPT_ADAM>), dim3(G), dim3(WS_THREADS), 0, s, sh, ep, jb);
+      break;
+    case OCF_OPT_ADADELTA:
+    case OCF_OPT_ADAMAX:
+      OCF_CHECK(g.s2, "optim_ws: Adadelta / Adamax need both slots");
+      launch_ws_x<CT>(g.opt.kind, G, sh, ep, jb, s);   // (instances in ocf_optim_ws_x.hip)
+      break;
+    default:
+      throw std::runtime_error("optim_ws: Adagrad, RMSprop, Adam, Adadelta or Adamax (kind " +
+                               std::to_string(g.opt.kind) + ")");
   }
   OCF_HIP(hipGetLastError());
+  ++g_optim_ws_count;
 }
 
 BiasActParams bias_act_params(const OcfGemmArgs& g) {
@@ -182,6 +193,7 @@ void dispatch_epi(const OcfGemmArgs& g, hipStream_t s) {
       if constexpr (!FP32_W || std::is_same<CT, float>::value) if constexpr (BCOL) {
         EpiOptim::Params p{g.p, g.s1, g.s2, g.ld_out, g.opt, g.p_shadow, g.compute_dtype, g.shadow_blocked != 0};
         OCF_CHECK(g.p != nullptr, "ocf_gemm OPTIM: p required");
+        check_opt(g.opt, g.s1, g.s2, "ocf_gemm OPTIM");
         OCF_CHECK((int64_t)g.M * g.ld_out * 4 < (int64_t(1) << 31), "ocf_gemm OPTIM: parameter block over 2 GiB");
         OCF_CHECK(!g.p_shadow || g.compute_dtype != OCF_F32, "ocf_gemm OPTIM: shadow weights need f16/bf16 compute");
         OCF_CHECK(!g.shadow_blocked || g.ld_out % 64 == 0, "ocf_gemm OPTIM: blocked shadow needs ld_out % 64 == 0");
@@ -195,7 +207,7 @@ void dispatch_epi(const OcfGemmArgs& g, hipStream_t s) {
             // role-split kernel for a dense A (16-bit, slots present -- SGD stays generic --, row-major B);
             // a sparse A goes to the row-stream kernel above or, without row lists, the generic kernel
             const bool ws_kind = g.opt.kind == OCF_OPT_ADAGRAD || g.opt.kind == OCF_OPT_RMSPROP ||
-                                 (g.opt.kind == OCF_OPT_ADAM && g.s2);
+                                 (opt_slots(g.opt.kind) == 2 && g.s2);
             if (optim_ws_on() && g.K <= g_optim_ws_max_k && ws_kind && g.s1 && !g.b_blocked && !g.a_sparse) {
               launch_ws<CT, false>(g, p, s);
               return;
@@ -281,6 +293,12 @@ extern "C" int ocf_set_tuning(const char* key, int value, int* previous) {
   } else if (k == "rows_dual_count") {    // read (previous) and reset the dual-row launch count
     if (previous) *previous = g_rows_dual_count;
     g_rows_dual_count = 0;
+  } else if (k == "rows_count") {         // read (previous) and reset the single row-stream launch count
+    if (previous) *previous = g_rows_count;
+    g_rows_count = 0;
+  } else if (k == "optim_ws_count") {     // read (previous) and reset the role-split launch count
+    if (previous) *previous = g_optim_ws_count;
+    g_optim_ws_count = 0;
   } else if (k == "rows_small_waves") {
     if (previous) *previous = g_rows_small_waves;
     g_rows_small_waves = value;

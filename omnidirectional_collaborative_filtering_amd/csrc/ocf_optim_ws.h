@@ -36,7 +36,7 @@ constexpr int WS_YS = GT_BN;                              // Y row stride (float
 constexpr int WS_HALF = 64;                               // rows of a wave's operand half
 // chunks per group and groups per tile (16 float4 chunks per stream thread per tile)
 template <int KIND> struct WsCfg {
-  static constexpr int NS = KIND == OCF_OPT_ADAM ? 2 : 1;   // optimizer slot streams
+  static constexpr int NS = opt_slots(KIND) == 2 ? 2 : 1;   // optimizer slot streams
   static constexpr int U = OCF_WS_U;
   static constexpr int NG = GT_BM * (GT_BN / 4) / GT_THREADS / U;
   static_assert(NG % 2 == 0, "groups alternate between two register sets");
@@ -606,5 +606,10 @@ optim_ws_kernel(GemmShape sh, EpiOptim::Params ep, WsJobs jobs) {
     }
   }
 }
+
+// the dense-A launch of the Adadelta / Adamax instances (ocf_optim_ws_x.hip; the other kinds' instances and the
+// launch arithmetic are ocf_gemm.hip's launch_ws): G workgroups of WS_THREADS
+template <typename CT>
+void launch_ws_x(int kind, int G, const GemmShape& sh, const EpiOptim::Params& ep, const WsJobs& jb, hipStream_t s);
 
 }  // namespace ocf

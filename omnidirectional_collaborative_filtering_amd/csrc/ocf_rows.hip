@@ -17,6 +17,7 @@ int g_rows_dual_parts = 0;   // dual-row launch: workgroups per 128-row tile (0:
 int g_rows_dual_pf = -1;   // dual-row launch: next row's chain issued ahead (-1: below 32 parts, 0 / 1: "rows_dual_pf")
 int g_rows_dual_large = 1;   // the dual-row launch on large weights too ("rows_dual_large"; 0: the pair launch there)
 int g_rows_dual_count = 0;   // dual-row launches since the last read ("rows_dual_count": tests see which form ran)
+int g_rows_count = 0;   // single row-stream launches (ocf_gemm) since the last read ("rows_count": tests see which kernel ran)
 int g_pair_wait_polls = 1 << 22;   // ocf_gemm_pair's bounded wait (ocf_set_tuning "pair_wait_polls"): seconds
 
 
@@ -36,6 +37,17 @@ WsJobs ws_jobs(const OcfGemmArgs& g) {
   j.jb_s1 = g.jb_s1; j.jb_s2 = g.jb_s2; j.jb_op = g.jb_op;
   j.js_sp = g.js_sp; j.js_rs = g.js_rs; j.js_out = g.js_out; j.js_nparts = g.js_nparts; j.js_ntiles = g.js_ntiles;
   j.js_M = g.js_M;
+  // the folded bias updates run the weight's kernel instance (its KIND), so their slots are checked for that kind
+  // as well as for the one their own parameter block names
+  OcfOptParams wk = g.opt;
+  if (g.cb_p) {
+    check_opt(g.cb_op, g.cb_s1, g.cb_s2, "ocf_gemm OPTIM (cb_op)");
+    check_opt(wk, g.cb_s1, g.cb_s2, "ocf_gemm OPTIM (cb_s1 / cb_s2 under the weight's optimizer)");
+  }
+  if (g.jb_part) {
+    check_opt(g.jb_op, g.jb_s1, g.jb_s2, "ocf_gemm OPTIM (jb_op)");
+    check_opt(wk, g.jb_s1, g.jb_s2, "ocf_gemm OPTIM (jb_s1 / jb_s2 under the weight's optimizer)");
+  }
   if (g.jr) {
     OCF_CHECK(g.jr->mode == OCF_REDUCE_GRAD_ACT && g.jr->part && g.jr->row_cptr && g.jr->h_out && g.jr->a_in &&
                   g.jr->H <= 512,
@@ -49,12 +61,12 @@ WsJobs ws_jobs(const OcfGemmArgs& g) {
 
 
 // EPI_OPTIM over a sparse batch operand given as row lists: the row-stream kernel (ocf_rows_dw.h),
-// one wave per weight row.  Takes 16-bit or fp32 compute, Adagrad / RMSprop / Adam with their slots, N a
+// one wave per weight row.  Takes 16-bit or fp32 compute, Adagrad / RMSprop / Adam / Adadelta / Adamax with their slots, N a
 // multiple of 128 up to 512 and a row-major shadow; anything else returns false (the tile kernels).
 bool rows_setup(const OcfGemmArgs& g, const EpiOptim::Params& ep, RowsLaunch& L) {
   // a lane's B elements are one 4-, 8- or 16-B load (16-bit or fp32 compute)
   const bool kind_ok = g.opt.kind == OCF_OPT_ADAGRAD || g.opt.kind == OCF_OPT_RMSPROP ||
-                       (g.opt.kind == OCF_OPT_ADAM && g.s2);
+                       ((g.opt.kind == OCF_OPT_ADAM || rows_kind_x(g.opt.kind)) && g.s2);
   if (!(kind_ok && g.s1 && g.N % 128 == 0 && g.N <= 512 && g.ldb >= g.N && g.ld_out == g.N && g.M % 128 == 0))
     return false;
   if (ep.shadow && ep.shadow_blocked) return false;

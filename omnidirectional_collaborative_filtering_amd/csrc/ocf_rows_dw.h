@@ -127,7 +127,7 @@ __device__ __forceinline__ void rowpipe_ranks(const RowsDwArgs& ra, const WsJobs
   using V = RsVec<CW>;
   using F = typename V::F;
   using H = RsH<CT, CW>;
-  constexpr bool ADAM = KIND == OCF_OPT_ADAM;
+  constexpr bool ADAM = opt_slots(KIND) == 2;   // two slot streams (Adam, Adadelta, Adamax)
   constexpr int E0 = RS_E0;
   using Row = RpRow<CT, CW, NCH, E0, ADAM, LONG>;
   const int lane = threadIdx.x & 63;
@@ -510,8 +510,8 @@ struct RdRow {
   int m, lo, n;
   int2 ev;                // the row's first 64 entries (lane i = entry i)
   float vo, vi;           // their output deltas / input values
-  F po[NCH], ao[NCH], bo[KIND == OCF_OPT_ADAM ? NCH : 1];
-  F pi[NCH], ai[NCH], bi[KIND == OCF_OPT_ADAM ? NCH : 1];
+  F po[NCH], ao[NCH], bo[opt_slots(KIND) == 2 ? NCH : 1];
+  F pi[NCH], ai[NCH], bi[opt_slots(KIND) == 2 ? NCH : 1];
   WsJobs::BiasPre bias;
 };
 
@@ -521,7 +521,7 @@ __global__ void __launch_bounds__(RS_THREADS) optim_rowdual_kernel(RowsDwArgs ro
   using V = RsVec<CW>;
   using F = typename V::F;
   using H = RsH<CT, CW>;
-  constexpr bool ADAM = KIND == OCF_OPT_ADAM;
+  constexpr bool ADAM = opt_slots(KIND) == 2;   // two slot streams (Adam, Adadelta, Adamax)
   using Row = RdRow<CT, KIND, CW, NCH>;
   const int bx = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const bool closed = gate_closed(ps);   // (consumed before this workgroup's first write)

@@ -22,8 +22,17 @@ bool rows_setup(const OcfGemmArgs& g, const EpiOptim::Params& ep, RowsLaunch& L)
 EpiOptim::Params optim_params(const OcfGemmArgs& g);
 bool rows_pair_ok(const OcfGemmArgs& g);
 
-// the kernel instance for (optimizer, N, parts, LONG): f(kernel template tag) launches it
-template <typename CT, typename F>
+// Adadelta / Adamax: their kernel instances live in ocf_rows_x_{f16,bf16,f32}.hip (ocf_rows_x.h), so the units
+// holding the Adagrad / RMSprop / Adam instances did not grow with them
+inline bool rows_kind_x(int kind) { return kind == OCF_OPT_ADADELTA || kind == OCF_OPT_ADAMAX; }
+template <typename CT> void rows_x_one(const RowsLaunch& L, hipStream_t s);
+template <typename CT> void rows_x_pair(const RowsLaunch& A, const RowsLaunch& B, const RsPair& ps, hipStream_t s);
+template <typename CT>
+void rows_x_dual(const RowsLaunch& A, const RowsLaunch& B, const RsPair& ps, int grid, hipStream_t s);
+
+// the kernel instance for (optimizer, N, parts, LONG): f(kernel template tag) launches it.  X: the Adadelta /
+// Adamax half of the kinds (rows_kind_x), else Adagrad / RMSprop / Adam; rows_setup admits no other kind
+template <typename CT, bool X, typename F>
 void rows_dispatch(const RowsLaunch& L, F&& f) {
   auto go = [&](auto kind_tag, auto cw_tag, auto nch_tag) {
     constexpr int KIND = decltype(kind_tag)::value, CW = decltype(cw_tag)::value;
@@ -42,10 +51,19 @@ void rows_dispatch(const RowsLaunch& L, F&& f) {
       default: go(k, integral_constant<int, 4>{}, integral_constant<int, 2>{});
     }
   };
-  switch (L.kind) {
-    case OCF_OPT_ADAGRAD: by_n(integral_constant<int, OCF_OPT_ADAGRAD>{}); break;
-    case OCF_OPT_RMSPROP: by_n(integral_constant<int, OCF_OPT_RMSPROP>{}); break;
-    default: by_n(integral_constant<int, OCF_OPT_ADAM>{});
+  if constexpr (X) {
+    switch (L.kind) {
+      case OCF_OPT_ADADELTA: by_n(integral_constant<int, OCF_OPT_ADADELTA>{}); break;
+      case OCF_OPT_ADAMAX: by_n(integral_constant<int, OCF_OPT_ADAMAX>{}); break;
+      default: throw std::runtime_error("row-stream dW: optimizer kind " + std::to_string(L.kind) + " has no instance");
+    }
+  } else {
+    switch (L.kind) {
+      case OCF_OPT_ADAGRAD: by_n(integral_constant<int, OCF_OPT_ADAGRAD>{}); break;
+      case OCF_OPT_RMSPROP: by_n(integral_constant<int, OCF_OPT_RMSPROP>{}); break;
+      case OCF_OPT_ADAM: by_n(integral_constant<int, OCF_OPT_ADAM>{}); break;
+      default: throw std::runtime_error("row-stream dW: optimizer kind " + std::to_string(L.kind) + " has no instance");
+    }
   }
 }
 
@@ -100,8 +118,10 @@ template <typename CT>
 bool launch_rows(const OcfGemmArgs& g, const EpiOptim::Params& ep, hipStream_t s) {
   RowsLaunch L;
   if (!rows_setup(g, ep, L)) return false;
-  rows_dispatch<CT>(L, RowsOne{L, s});
+  if (rows_kind_x(L.kind)) rows_x_one<CT>(L, s);
+  else rows_dispatch<CT, false>(L, RowsOne{L, s});
   OCF_HIP(hipGetLastError());
+  ++g_rows_count;
   return true;
 }
 
@@ -147,10 +167,12 @@ bool launch_rows_pair(const OcfGemmArgs& a, const OcfGemmArgs& b, OcfPairSync& s
     if (g_rows_dual_parts) parts = g_rows_dual_parts;
     ps.parts = parts;
     const int grid = nprod + (B.jb.count() + 3) / 4 + A.ra.M / 128 * parts;
-    rows_dispatch<CT>(A, RowsDual{A, B, ps, grid, s});
+    if (rows_kind_x(A.kind)) rows_x_dual<CT>(A, B, ps, grid, s);
+    else rows_dispatch<CT, false>(A, RowsDual{A, B, ps, grid, s});
     ++g_rows_dual_count;
   } else {
-    rows_dispatch<CT>(A, RowsPair{A, B, ps, s});
+    if (rows_kind_x(A.kind)) rows_x_pair<CT>(A, B, ps, s);
+    else rows_dispatch<CT, false>(A, RowsPair{A, B, ps, s});
   }
   OCF_HIP(hipGetLastError());
   sync.count = ps.want;

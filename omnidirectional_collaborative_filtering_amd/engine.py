@@ -291,6 +291,9 @@ class Engine:
         return self.loss.grad_num / ((self.rows_real or self.B) * self.N_total)
 
     def set_optimizer(self, opt):
+        if self.comm is not None or self.dp_world > 1:
+            from . import optimizers
+            optimizers.check_single_gpu(opt, "the feature-parallel / data-parallel layouts")
         self.opt = opt
         self._bufgen += 1
         self.slots = []
@@ -1871,7 +1874,7 @@ class Engine:
         (forward), stats slot, optimizer constants (Keras decay / Adam bias correction)"""
         row = self.stats_hist.data_ptr() + self.n_stats * self.stats_hist.stride(0) * 4
         stream = (self.step_count * self.dp_world + self.dp_rank) * 16
-        if self.opt.kind != _lib.OPT_ADAM and not self.opt.decay and self._plan is not None \
+        if not self.opt.scalars_change and self._plan is not None \
                 and self._plan.get("ready"):
             return stream, row, None, None     # constant optimizer scalars: the template's stand
         gscale = self._gscale()
@@ -2052,7 +2055,7 @@ class Engine:
                 and len(self.H) == 1 and self.sparse_ok and self.use_sparse and self.sparse_dw
                 and self.epoch_row_lists and self.epoch_scatter and not self.l2
                 and all(self.trainable) and self.grad_hook is None and self.master_sync is None
-                and self.opt.kind != _lib.OPT_ADAM and not self.opt.decay):
+                and not self.opt.scalars_change):
             return None
         return (tok, self._bufgen, id(self.opt), self.opt.lr, getattr(self.opt, "epsilon", 0.0), self.row_skip,
                 self.shadow_blocked, self.keep, self.seed, self.act, id(self.comm),

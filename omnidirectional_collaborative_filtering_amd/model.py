@@ -69,6 +69,8 @@ class Model(object):
         if int(world) > 1 and self.loss.code != losses.MeanSquaredError.code:
             raise NotImplementedError("loss %r is not implemented under data parallelism (only "
                                       "'mean_squared_error' is)" % (self.loss.name,))
+        if int(world) > 1 and self.optimizer is not None:
+            optimizers.check_single_gpu(self.optimizer, "data parallelism")
         if self.engine.comm is not None:
             raise ValueError("data parallelism over a feature-parallel (column-sharded) engine is not supported")
         self.rank, self.world = int(rank), int(world)
@@ -76,6 +78,8 @@ class Model(object):
 
     def enable_feature_parallel(self, rank, world):
         """record the column-shard layout (the engine was built with shard=/comm=) for checkpoints"""
+        if int(world) > 1 and self.optimizer is not None:
+            optimizers.check_single_gpu(self.optimizer, "feature parallelism")
         self.fp = (int(rank), int(world))
 
     def _train_one(self, gen):
@@ -114,10 +118,15 @@ class Model(object):
         if loss.code != losses.MeanSquaredError.code and self.dp is not None:
             raise NotImplementedError("loss %r is not implemented under data parallelism (only "
                                       "'mean_squared_error' is)" % (loss.name,))
+        optimizer = optimizers.get(optimizer)
+        if self.dp is not None:
+            optimizers.check_single_gpu(optimizer, "data parallelism")
+        if self.fp is not None and self.fp[1] > 1:
+            optimizers.check_single_gpu(optimizer, "feature parallelism")
         self.engine.set_loss(loss)
         self.loss = loss
-        self.optimizer = optimizers.get(optimizer)
-        self.engine.set_optimizer(self.optimizer)
+        self.engine.set_optimizer(optimizer)
+        self.optimizer = optimizer
         self.metric_names = [M.metric_name(m) for m in (metrics or [])]
         if rating_range is not None:
             self.rating_range = float(rating_range)
@@ -628,6 +637,9 @@ class Model(object):
                     if t is not None:
                         tensors["opt/b%d/%d" % (i, j)] = t.cpu().numpy()
             tensors["opt/iterations"] = np.array([self.optimizer.iterations], np.int64)
+            # whose slots these are: the two-slot kinds give them different meanings (Adam's v, Adadelta's d,
+            # Adamax's u), so a load into another optimizer must not reinterpret them
+            tensors["opt/name"] = np.frombuffer(self.optimizer.name.encode("ascii"), np.uint8).copy()
         # the objective, with the optimizer state: a resumed run must not silently switch it
         tensors["loss/name"] = np.frombuffer(self.loss.name.encode("ascii"), np.uint8).copy()
         tensors["loss/param"] = np.array([self.loss.param], np.float64)
@@ -636,6 +648,14 @@ class Model(object):
     def load(self, path, with_optimizer=True):
         from safetensors.numpy import load_file
         t = load_file(self.shard_path(path))
+        opt_state = with_optimizer and self.optimizer is not None and "opt/iterations" in t
+        # whose slots the file holds, before anything of the model changes: a refused load leaves it as it was
+        if opt_state and "opt/name" in t:     # (a file from before the field: loads as it always did)
+            name = bytes(bytearray(t["opt/name"].astype(np.uint8))).decode("ascii")
+            if name != self.optimizer.name:
+                raise ValueError("%s holds the optimizer state of %r, this model is compiled with %r: load it "
+                                 "with with_optimizer=False or compile the model with %r"
+                                 % (path, name, self.optimizer.name, name))
         n = len([k for k in t if k.startswith("param/")])
         self.set_weights([t["param/%d" % i] for i in range(n)])
         e = self.engine
@@ -644,7 +664,7 @@ class Model(object):
             saved = self.saved_loss(t)
             e.set_loss(saved)
             self.loss = saved
-        if with_optimizer and self.optimizer is not None and "opt/iterations" in t:
+        if opt_state:
             for i, (sw, sb) in enumerate(e.slots):
                 for j, s in enumerate(sw):
                     if s is not None:

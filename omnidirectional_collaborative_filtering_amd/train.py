@@ -36,7 +36,7 @@ DEFAULTS = dict(
     shuffle_data_every_epoch=True, val_split=[0.8, 0.1, 0.1], useJSON=True, early_stopping_metric="val_accurate_MSE",
     eval_mode="fixed_split", l2_weight_regulatization=None, pass_through_input_training=True, dropout_probability=0.2,
     numlayers=1, num_hidden_units=512, use_causal_info=False, auxilliary_mask_type=None, aux_var_value=-1,
-    model_save_path="models/", model_loss="mean_squared_error", learning_rate=0.005, optimizer="adagrad",
+    model_save_path="models/", model_loss="mean_squared_error", learning_rate=None, optimizer="adagrad",
     activation_type="sigmoid", use_sparse_representation=False, use_experimental_sparse_masking_layer=False,
     load_weights_from=None, perform_finetuning=False, compute_dtype="float32", metadata="./datasets_metadata.json",
     synthetic=None, seed=None, rng="numpy", parallel="feature", dp_mode="sharded", dp_grad_dtype="float32",
@@ -46,6 +46,13 @@ DEFAULTS = dict(
     # rank 0 after the manual test leg (Model.predict_entries); clip_predictions: [lo, hi] clips them to the rating range
     save_test_predictions=None, clip_predictions=None,
 )
+
+
+OPTIMIZERS = ("adagrad", "rmsprop", "adam", "adadelta", "adamax")
+# learning_rate None (the default, on the command line and in DEFAULTS) means not given: the reference's 0.005 for
+# the optimizers it trains with, Keras' own default for Adadelta (built around lr = 1) and Adamax (0.002)
+REFERENCE_LR = 0.005
+KERAS_LR = {"adadelta": 1.0, "adamax": 0.002}
 
 
 def shard_donor_weights(weights, c0, c1, n_total, k=1):
@@ -111,6 +118,11 @@ def run(cfg):
     from .model import omni_model
     from .parallel import init_from_env
     from .parallel import feature_shard_range, make_comm
+    cfg = dict(cfg, optimizer=str(cfg["optimizer"]).lower())
+    if cfg["optimizer"] not in OPTIMIZERS:
+        raise ValueError("optimizer must be one of %s (got %r)" % (", ".join(OPTIMIZERS), cfg["optimizer"]))
+    if cfg.get("learning_rate") is None:      # not given: the reference's 0.005, or Keras' own default
+        cfg["learning_rate"] = KERAS_LR.get(cfg["optimizer"], REFERENCE_LR)
     rank, world, local = init_from_env()
     import torch
     torch.cuda.set_device(local)
@@ -167,7 +179,9 @@ def run(cfg):
     m = om.model
     opt = {"adagrad": lambda: O.Adagrad(lr=cfg["learning_rate"], epsilon=1e-08, decay=0.0),
            "rmsprop": lambda: O.RMSprop(lr=cfg["learning_rate"]),
-           "adam": lambda: O.Adam(lr=cfg["learning_rate"])}[cfg["optimizer"]]()
+           "adam": lambda: O.Adam(lr=cfg["learning_rate"]),
+           "adadelta": lambda: O.Adadelta(lr=cfg["learning_rate"]),
+           "adamax": lambda: O.Adamax(lr=cfg["learning_rate"])}[cfg["optimizer"]]()
     loss_name = str(cfg["model_loss"]).lower()
     m.compile(opt, loss_name, loss_params={"delta": cfg.get("huber_delta", 1.0)} if loss_name == "huber" else None,
               metrics=["mae", "accurate_MAE", "nMAE", "accurate_RMSE", "accurate_MSE"])
