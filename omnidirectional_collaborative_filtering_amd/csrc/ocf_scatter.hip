@@ -94,15 +94,12 @@ __device__ __forceinline__ void scatter_entry(const ScatterArgs& a, const int64_
     }
     const int64_t o = (int64_t)b * a.ld + c;
     const int64_t ox = (int64_t)b * a.xin_ld + c;
+    const bool live_in = (role & 1) && !later_in;
     if (role & 1) {
       if (a.Min) a.Min[o] = aux;
-      if (!later_in) {
-        if (a.X) a.X[o] = v;
-        if (a.xin) store_val(a.xin, a.xin_dtype, ox, v);
-      }
-      if (a.xin && a.feed == 1) store_val(a.xin, a.xin_dtype, ox + xb, aux);
+      if (live_in && a.X) a.X[o] = v;
     }
-    if (a.xval1) a.xval1[e] = ((role & 1) && !later_in) ? v : 0.f;
+    if (a.xval1) a.xval1[e] = live_in ? v : 0.f;
     if (a.tb_cnt) atomicAdd(&a.tb_cnt[(c >> 7) * a.tb_nk + (b >> 6)], 1);   // ocf_sparse_tiles counts
     if (a.col_cnt) {                                                         // ocf_row_lists counts / keys
       atomicAdd(&a.col_cnt[c], 1);
@@ -116,10 +113,14 @@ __device__ __forceinline__ void scatter_entry(const ScatterArgs& a, const int64_
     }
     if (a.tflag1) a.tflag1[e] = live_tg ? 1 : 0;
     // row tags (ocf.h OcfScatterArgs rtag_*): same-value byte stores, no ordering needed
-    if (a.rtag_in && (role & 1) && !later_in) a.rtag_in[c] = (uint8_t)a.rtag;
+    if (a.rtag_in && live_in) a.rtag_in[c] = (uint8_t)a.rtag;
     if (a.rtag_out && live_tg) a.rtag_out[c] = (uint8_t)a.rtag;
     if (a.Mmiss) a.Mmiss[o] = aux;
+    // every xin store of the entry under this one test of the pointer: a compiler workaround (with the rating's
+    // store in a branch of its own, a bf16 xin lost its M_in block), guarded by test_scatter_direct_gpu.py test_xin
     if (a.xin) {
+      if (live_in) store_val(a.xin, a.xin_dtype, ox, v);
+      if ((role & 1) && a.feed == 1) store_val(a.xin, a.xin_dtype, ox + xb, aux);
       if (a.feed == 2) store_val(a.xin, a.xin_dtype, ox + xb, aux);
       if (a.both) store_val(a.xin, a.xin_dtype, ox + 2 * xb, aux);
     }
@@ -439,6 +440,14 @@ extern "C" int ocf_scatter_batch(const ScatterArgs* args, void* stream) {
             "ocf_scatter_batch: col_cnt needs ecb, mode 0, B <= 4096 and N <= 2^19");
   OCF_CHECK(!(a.rtag_in || a.rtag_out) || (a.rtag >= 1 && a.rtag <= 255),
             "ocf_scatter_batch: row tags need 1 <= rtag <= 255");
+  // the offset table of the largest admitted batch (16,384 rows: 131,080 bytes) is past the default 64 KB of
+  // dynamic LDS a launch may ask for (checked before anything is enqueued)
+  static const bool lds_attr =
+      hipFuncSetAttribute((const void*)scatter_flat_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (16384 + 1) * (int)sizeof(int64_t)) == hipSuccess &&
+      hipFuncSetAttribute((const void*)bucket_fill_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (16384 + 1) * (int)sizeof(int64_t)) == hipSuccess;
+  OCF_CHECK(lds_attr, "ocf_scatter_batch: cannot raise the dynamic LDS limit");
   // zero rows [0, B_pad) of every dense output (contiguous [B_pad][ld] blocks); outputs that sit back to back
   // in memory are cleared by one memset (each memset is a launch of its own)
   {
